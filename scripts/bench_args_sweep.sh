@@ -4,7 +4,7 @@
 OUT=${1:-gpurun_out/bench_args}; mkdir -p $OUT
 for sw in "1 0" "1 1" "2 0" "15 0" "16 0" "17 0" "31 1" "32 0" "33 16" "48 17" "20 5" "64 3" "100 0"; do
   set -- $sw
-  python3 bench.py --steps $1 --warmup $2 --no-also --no-end-to-end --no-cpu-baseline > $OUT/s$1_w$2.json 2> $OUT/s$1_w$2.err; rc=$?
+  python3 bench.py --full --steps $1 --warmup $2 --no-also --no-end-to-end --no-cpu-baseline > $OUT/s$1_w$2.json 2> $OUT/s$1_w$2.err; rc=$?
   python3 - "$OUT/s$1_w$2.json" $rc $1 $2 <<'PY'
 import json, sys
 f, rc, s, w = sys.argv[1], int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])

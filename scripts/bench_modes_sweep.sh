@@ -3,7 +3,7 @@
 # line, parity green.   usage: scripts/bench_modes_sweep.sh <outdir>
 OUT=${1:-gpurun_out/bench_modes}; mkdir -p $OUT
 run() {
-  tag=$(echo "$*" | tr ' -' '__'); python3 bench.py "$@" --no-also --no-end-to-end --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err; rc=$?
+  tag=$(echo "$*" | tr ' -' '__'); python3 bench.py --full "$@" --no-also --no-end-to-end --no-cpu-baseline > $OUT/$tag.json 2> $OUT/$tag.err; rc=$?
   python3 - "$OUT/$tag.json" $rc "$*" <<'PY'
 import json, sys
 f, rc, args = sys.argv[1], int(sys.argv[2]), sys.argv[3]

@@ -4,16 +4,17 @@
 # configs 2 / 5 and the ring through kbench (scripts/collect_profiles_cfg.sh), directional pipeline, legacy stream, power probe.
 #   usage: scripts/evidence.sh <tag>          -> gpurun_out/<tag>*/ ; afterwards: scripts/refresh_profiles.sh <round> <tag>
 set -o pipefail
+REPO=$(cd "$(dirname "$0")/.." && pwd)
 cd /root/repo
 TAG=${1:-ev}
 OUT=/root/repo/gpurun_out/$TAG
 mkdir -p $OUT
-python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
-python bench.py --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench_driver_args.err || exit 1
+python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || exit 1
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_args.json 2> $OUT/bench_driver_args.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 # (--no-also: the appended legs launch the SAME kernel on other workloads and would blur the average)
-rocprofv3 --kernel-trace --stats -d $OUT/kt_default -o p --output-format csv -- python3 /root/repo/bench.py --no-cpu-baseline --no-also > $OUT/bench_default_under_profiler.json 2> $OUT/kt_default.log || exit 1
-rocprofv3 --kernel-trace --stats -d $OUT/kt_c4 -o p --output-format csv -- python3 /root/repo/bench.py --config 4 --no-cpu-baseline --no-end-to-end --no-also > $OUT/bench_c4_under_profiler.json 2> $OUT/kt_c4.log || exit 1
+rocprofv3 --kernel-trace --stats -d $OUT/kt_default -o p --output-format csv -- python3 $REPO/bench.py --full --no-cpu-baseline --no-also > $OUT/bench_default_under_profiler.json 2> $OUT/kt_default.log || exit 1
+rocprofv3 --kernel-trace --stats -d $OUT/kt_c4 -o p --output-format csv -- python3 $REPO/bench.py --full --config 4 --no-cpu-baseline --no-end-to-end --no-also > $OUT/bench_c4_under_profiler.json 2> $OUT/kt_c4.log || exit 1
 echo "kernel traces done"
 B="python3 /root/repo/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-end-to-end --no-also"
 for c in FETCH_SIZE WRITE_SIZE; do

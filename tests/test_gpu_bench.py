@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,7 +19,7 @@ def _json_line(out: str) -> dict:
 
 
 def test_bench_single_gpu_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "19", "--warmup", "3", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "19", "--warmup", "3", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -70,8 +71,52 @@ def test_bench_single_gpu_contract():
     assert e2e["paper_philox_metrics_only"]["evals"] == 4 * 11 * 1000 * 100 and e2e["c4_level_api"]["evals"] == 10**8
 
 
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run as a driver types it (no --full): the headline line and nothing else, and with --dump-outputs what the
+    last timed step computed - the same arrays from two runs with the same arguments, and the right ones: step 19 of 19 read
+    draw tensor 18 % 3 = 0 (bench.py's inputs restated here), checked on a subsample against the oracle."""
+    from oracle import robchar_oracle as orc
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"dump{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "19", "--warmup", "3",
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _json_line(r.stdout)
+        assert d["metric"].startswith("MC fidelity evals/sec") and d["unit"] == "evals/s" and d["higher_is_better"] is True
+        assert d["dtype"] == "f64" and d["steps"] == 19 and d["warmup"] == 3 and d["n_gpus"] == 1
+        assert abs(d["value"] - 1e6 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+        assert d["cpu_baseline"] is None and d["end_to_end"] is None and "also" not in d and "check" not in d
+        assert sorted(f.name for f in out.iterdir()) == ["fidelity.npy", "min.npy", "q.npy", "rim1.npy", "std.npy"]
+        assert sum(f.stat().st_size for f in out.iterdir()) <= 64 << 20
+        dumps.append({f.stem: np.load(f) for f in out.iterdir()})
+    got = dumps[0]
+    for name, a in got.items():
+        assert a.dtype == np.float64 and np.array_equal(a, dumps[1][name], equal_nan=True), name
+    fid = got["fidelity"]
+    assert fid.shape == (100, 10000) and got["rim1"].shape == (3, 100) and got["q"].shape == (3, 2, 100)
+    rng = np.random.default_rng(20220714 + 3)
+    ctrl = np.empty((100, 8))
+    ctrl[:, :7] = rng.uniform(-10, 10, (100, 7))
+    ctrl[:, 7] = rng.uniform(2, 30, 100)
+    rs = np.random.RandomState(12345)
+    rs.normal(scale=0.05)
+    draws = 0.05 * rs.standard_normal((100, 10000, 7, 3))
+    rows, cols = np.arange(0, 100, 12), np.arange(0, 10000, 997)
+    want = orc.fidelity_eigh(ctrl[rows], draws[rows][:, cols], 7, 0, 6)
+    assert np.abs(fid[rows][:, cols] - want).max() < 1e-10
+    eps = orc.compute_dkw_error(0.05, 10000)               # the metrics: the oracle's reductions of the dumped fidelities
+    for v, data in enumerate([fid, np.clip(fid - eps, 0, 1), np.clip(fid + eps, 0, 1)]):
+        rows_v = orc.metric_rows(data)
+        assert np.abs(got["rim1"][v] - rows_v[orc.METRIC_NAMES[0]]).max() < 1e-10
+        assert np.array_equal(-got["q"][v, 0], rows_v[orc.METRIC_NAMES[1]])
+        assert np.array_equal(-got["q"][v, 1], rows_v[orc.METRIC_NAMES[2]])
+        assert np.abs(got["std"][v] - rows_v[orc.METRIC_NAMES[3]]).max() < 1e-10
+        assert np.array_equal(-got["min"][v], rows_v[orc.METRIC_NAMES[4]])
+
+
 def test_bench_config4_explicit():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "4", "--steps", "6", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "4", "--steps", "6", "--warmup", "2",
                         "--no-end-to-end"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -86,7 +131,7 @@ def test_bench_config4_with_draws_generated_in_the_kernel():
     same stream elements as `--config 4` generates once, so the LAST step's metric table equals config 4's bit for bit."""
     out = {}
     for cfg in ("40", "4"):
-        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", cfg, "--steps", "3", "--warmup", "1",
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", cfg, "--steps", "3", "--warmup", "1",
                             "--no-end-to-end", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, cwd=ROOT)
         assert r.returncode == 0, r.stderr[-2000:]
         out[cfg] = _json_line(r.stdout)
@@ -101,7 +146,7 @@ def test_bench_config4_with_draws_generated_in_the_kernel():
 @pytest.mark.parametrize("config,evals,kernel", [(2, 10**6, "<5, 2>"), (5, 10**6, "<10, 2>")])
 def test_bench_other_baseline_configs(config, evals, kernel):
     """BASELINE configs 2 (N = 5) and 5 (N = 10 XXZ) as bench modes: same contract, CPU baseline on the whole workload."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", str(config), "--steps", "40", "--warmup", "5",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", str(config), "--steps", "40", "--warmup", "5",
                         "--no-end-to-end"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = _json_line(r.stdout)
@@ -114,7 +159,7 @@ def test_bench_other_baseline_configs(config, evals, kernel):
 def test_bench_two_ranks_gloo_rehearsal():
     env = dict(os.environ, ROBCHAR_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
-                        "--master-addr", "127.0.0.1", "--master-port", "29571", os.path.join(ROOT, "bench.py"),
+                        "--master-addr", "127.0.0.1", "--master-port", "29571", os.path.join(ROOT, "bench.py"), "--full",
                         "--gpus", "2", "--steps", "11", "--warmup", "3"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
@@ -136,7 +181,7 @@ def test_bench_single_rank_rccl_branch():
     `all_gather_into_tensor` on the high-priority side stream, scatter / broadcast of the legacy-stream state."""
     env = dict(os.environ, ROBCHAR_BENCH_FORCE_PG="1", ROBCHAR_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29573",
                RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "35", "--warmup", "3", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "35", "--warmup", "3", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _json_line(r.stdout)
@@ -153,7 +198,7 @@ def test_bench_extras_watchdog_keeps_the_headline():
     the ONE line is still printed - headline intact, the unfinished extras marked, the leg in flight named - and the
     exit code is the distinct EXIT_EXTRAS (3), not 0: a hang in the extras is visible to whoever reads the rc."""
     env = dict(os.environ, ROBCHAR_BENCH_EXTRAS_TIMEOUT_S="0.05")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "20", "--warmup", "5", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert r.returncode == 3, (r.stdout + r.stderr)[-3000:]
     d = _json_line(r.stdout)
@@ -169,7 +214,7 @@ def test_bench_self_launch_two_ranks():
     The line proves what the communicator saw (`config.rccl`) and carries both exchange variants of config 4."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["ROBCHAR_BENCH_BACKEND"] = "gloo"
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5"],
                        capture_output=True, text=True, timeout=1100, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _json_line(r.stdout)
@@ -193,7 +238,7 @@ def test_bench_self_launch_two_gpus_rccl():
     if torch.cuda.device_count() < 2:
         pytest.skip("needs two GPUs")
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "ROBCHAR_BENCH_BACKEND")}
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "20", "--warmup", "5"],
                        capture_output=True, text=True, timeout=1100, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     d = _json_line(r.stdout)
@@ -207,7 +252,7 @@ def test_bench_self_launch_two_gpus_rccl():
 def _self_launched(extra_args, nranks, timeout=1100):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env["ROBCHAR_BENCH_BACKEND"] = "gloo"
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py")] + (["--gpus", str(nranks)] if nranks > 1 else []) + extra_args
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full"] + (["--gpus", str(nranks)] if nranks > 1 else []) + extra_args
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, cwd=ROOT, env=env)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     return _json_line(r.stdout)
