@@ -11,6 +11,7 @@ import pickle
 import numpy as np
 import pytest
 
+import chain_checks as cc
 from conftest import highfid_workload, load_json
 from gpu_common import rand_ctrl, _h0
 from oracle import philox_host
@@ -93,6 +94,8 @@ def test_random_vs_oracle_all_N(be, N):
     got = be.mc_fidelity(ctrl, draws, N, a, b, h0_diag=orc.xxz_delta(N))
     want = orc.fidelity_eigh(ctrl, draws, N, a, b, h0_diag=orc.xxz_delta(N))
     assert np.abs(got - want).max() < TOL
+    # rand_ctrl's rows are localised (for N >= 9 the end-to-end comparison above leans on row 0 alone): delocalised rows too
+    cc.check_deloc_vs_oracle(be, N)
 
 
 @pytest.mark.parametrize("K", [1, 2, 63, 64, 65, 128, 1000])
@@ -165,6 +168,29 @@ def test_general_path_is_exercised(be):
         assert be.general_path_tiles() == 0                # an exactly cancelled coupling enters as 1e-150: fast path
         sel = slice(0, 400)
         assert np.abs(got[:, sel] - orc.fidelity_eigh(ctrl, draws[:, sel], N, a, b)).max() < TOL
+    # (3) pairs INSIDE one half of the cut chain, where the degenerate samples' answer is not 0, on delocalised rows; odd N
+    # cut on both sides of the middle site.  N >= 17: no in-register repair - bad lanes go straight to the LDS routine
+    for N in (4, 10, 16, 17, 20, 24):
+        C, K, cut = 3, 128, N // 2
+        ctrl = cc.deloc_ctrl(rng, C, N, 0.5)
+        ctrl[:, N] = rng.uniform(0.3 * N, 0.5 * N, C)
+        ctrl[:, N - cut:N] = ctrl[:, :cut][:, ::-1]
+        draws = 0.05 * rng.standard_normal((C, K, N, 3))
+        draws[:, ::5, :, 0] = 0.0
+        for c in range(cut, N - cut + 1):
+            draws[:, ::5, c, 1] = -1.0
+            draws[:, ::5, c, 2] = 0.0
+        for i in range(1, cut):
+            draws[:, ::5, N - i, 1:] = draws[:, ::5, i, 1:]
+        for (a, b, kern) in ((0, cut - 1, "auto"), (1, 1, "tridiag_adj"), (N - 1, N - cut, "auto")):
+            be.general_path_tiles(reset=True)
+            got = be.mc_fidelity(ctrl, draws, N, a, b, kernel=kern)
+            tiles = be.general_path_tiles()
+            print(f"general path, N = {N}, ({a}, {b}) {kern}: {tiles} tiles of {C * K // 64}")
+            assert tiles == C * K // 64, (N, a, b, tiles)
+            want = orc.fidelity_eigh(ctrl, draws, N, a, b)
+            cc.assert_has_teeth(want[:, ::5], what=(N, a, b, "degenerate samples"))
+            cc.compare(got, want, (N, a, b, kern))
 
 
 @pytest.mark.parametrize("N", [4, 5, 7, 10])
@@ -193,9 +219,14 @@ def test_near_degenerate_spectra_eigenvalue_only_modes(be, N):
     assert worst < 1e-11, worst
 
 
-@pytest.mark.parametrize("N", [17, 24, 32])
+_LONG_WORST = {"17-24": cc.Worst(), "25-32": cc.Worst()}
+
+
+@pytest.mark.parametrize("N", list(range(17, 33)))
 def test_long_chains_general_kernel(be, N):
-    """16 < N <= 32: the LDS-resident general kernel (chain topology only); ragged K, a NaN row, XXZ offsets."""
+    """16 < N <= 32: the register-resident adjugate kernel (17 .. 24) and the LDS-resident general kernel (chain topology
+    only); ragged K, a NaN row, XXZ offsets.  The rand_ctrl rows below are localised (end-to-end fidelities down to 1e-26):
+    tests/chain_checks.py holds every route to delocalised rows as well."""
     rng = np.random.default_rng(7000 + N)
     C, K = 4, 150
     ctrl = rand_ctrl(rng, C, N)
@@ -214,6 +245,18 @@ def test_long_chains_general_kernel(be, N):
         be.mc_fidelity(ctrl, draws, N, 0, N - 1, kernel="expm")
     with pytest.raises(Exception):
         be.mc_fidelity(rand_ctrl(rng, 2, 33), np.zeros((2, 4, 33, 3)), 33, 0, 32)
+    worst = _LONG_WORST["17-24" if N <= 24 else "25-32"]
+    cc.check_long_chain(be, N, worst)
+    print(f"long chains N = 17 ... {N}: " + " | ".join(f"{k}: {v}" for k, v in _LONG_WORST.items()))
+
+
+@pytest.mark.parametrize("N", list(range(2, 33)))
+def test_closed_form_chain_every_kernel(be, N):
+    """The spin-j chain (H = lam Jx + g Jz: non-unit h0_offdiag, fidelities in closed form) from both ends to every site,
+    every kernel that accepts N, T from 0 to the first full transfer."""
+    worst = cc.Worst()
+    cc.check_closed_form(be, N, worst)
+    print(f"closed form N = {N}: {worst}")
 
 
 @pytest.mark.parametrize("N", [2, 3, 5, 7, 10, 16])
@@ -270,6 +313,8 @@ def test_random_configs_all_kernels(be, seed):
         for kern in ("auto", "tridiag_ql", "tridiag_adj", "jacobi"):
             got = be.mc_fidelity(ctrl, draws, N, a, b, h0_diag=h0, kernel=kern)
             assert np.abs(got - want).max() < TOL, (N, a, b, sigma, kern)
+    # as many configurations again on delocalised rows, N up to 32 (most of the ones above have max F < 1e-3)
+    cc.check_random_deloc_configs(be, seed)
 
 
 def test_torch_device_pointer_path(be):

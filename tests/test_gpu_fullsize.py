@@ -11,6 +11,7 @@ import pickle
 import numpy as np
 import pytest
 
+from chain_checks import compare
 from conftest import highfid_workload, load_json
 from gpu_common import rand_ctrl
 from oracle import philox_host
@@ -18,18 +19,6 @@ from oracle import robchar_oracle as orc
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-10
-REL = 1e-9           # relative bound on samples with F > 1e-3 (measured: ~1e-13)
-
-
-def compare(got, want, what):
-    """absolute bound everywhere, relative bound where the fidelity is not tiny; returns (max abs, max rel, share F > 1e-3)"""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    err = np.abs(got - want)
-    big = want > 1e-3
-    rel = float((err[big] / want[big]).max()) if big.any() else 0.0
-    assert err.max() < TOL, (what, float(err.max()))
-    assert rel < REL, (what, rel)
-    return float(err.max()), rel, float(big.mean())
 
 
 def oracle_chunked(ctrl, draws, N, a, b, h0, chunk=2000):

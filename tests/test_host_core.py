@@ -865,3 +865,91 @@ def test_wave_emulation_ring_tiles_vs_oracle(wave, N):
                 assert np.abs(fid - want).max() < 2e-11, (N, trial, a, b, route, np.abs(fid - want).max())
                 listed += int(route == 0 and (rep > 0).any())
     assert listed > 0                                              # the repair wave did run
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# chains of 17 .. 24 spins: the arithmetic of mc_fid_chain_kernel<N, kWeightsAdjugate> (robchar_large.hip) on the host
+# ------------------------------------------------------------------------------------------------------------------------
+
+LONG_N = list(range(17, 25))
+
+
+@pytest.fixture(scope="module")
+def host_long(tmp_path_factory):
+    """tests/host/host_long.cpp once per N (one translation unit each, compiled in parallel)"""
+    d = tmp_path_factory.mktemp("hostlong")
+    src = os.path.join(ROOT, "tests", "host", "host_long.cpp")
+    procs = {n: subprocess.Popen(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", f"-DRC_HOST_N={n}", "-o",
+                                  str(d / f"librc_hostlong{n}.so"), src]) for n in LONG_N}
+    assert all(p.wait() == 0 for p in procs.values())
+    libs = {}
+    for n in LONG_N:
+        lib = ctypes.CDLL(str(d / f"librc_hostlong{n}.so"))
+        lib.rc_host_long_general_calls.restype = ctypes.c_longlong
+        assert lib.rc_host_long_n() == n
+        libs[n] = lib
+
+    def fid(ctrl, draws, N, a, b, h0d=None, h0o=None):
+        C, K = draws.shape[:2]
+        ctrl = np.ascontiguousarray(ctrl, dtype=np.float64)
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        h0d = np.zeros(N) if h0d is None else np.ascontiguousarray(h0d, dtype=np.float64)
+        h0o = np.ones(N - 1) if h0o is None else np.ascontiguousarray(h0o, dtype=np.float64)
+        res = np.empty((C, K))
+        assert libs[N].rc_host_long_chain_fidelity(N, ctrl.ctypes.data_as(P), h0d.ctypes.data_as(P), h0o.ctypes.data_as(P),
+                                                   draws.ctypes.data_as(P), ctypes.c_longlong(C), ctypes.c_longlong(K), a, b,
+                                                   res.ctypes.data_as(P)) == 0
+        return res
+    fid.general_calls = lambda N: libs[N].rc_host_long_general_calls()
+    return fid
+
+
+@pytest.mark.parametrize("N", LONG_N)
+def test_long_chain_core_vs_closed_form_and_oracle(host_long, N):
+    """The spin-j chain (non-unit couplings, closed form) from both ends to every site, and delocalised controllers (end to
+    end, interior, a = b, XXZ) against the oracle - absolute 1e-10 and relative 1e-9, on inputs with teeth; no sample of
+    these leaves the fast path."""
+    import chain_checks as cc
+    g0 = host_long.general_calls(N)
+    ctrl = cc.closed_form_ctrl(N, cc.CF_GS, cc.CF_TS)
+    off = cc.closed_form_offdiag(N)
+    draws = np.zeros((ctrl.shape[0], 1, N, 3))
+    for a in (0, N - 1):
+        for b in range(N):
+            cc.compare(host_long(ctrl, draws, N, a, b, h0o=off)[:, 0], cc.closed_form_fid(N, ctrl, a, b), (N, a, b, "closed form"))
+    rng = np.random.default_rng(5100 + N)
+    ctrl = np.concatenate([cc.deloc_ctrl(rng, 3, N, W) for W in (0.2, 0.5, 1.0)])
+    draws = 0.05 * rng.standard_normal((9, 40, N, 3))
+    for (a, b, h0) in ((0, N - 1, None), (N - 1, 0, None), (2, N // 2, None), (N // 2, N // 2, None), (0, N - 1, orc.xxz_delta(N))):
+        want = orc.fidelity_eigh(ctrl, draws, N, a, b, h0_diag=h0)
+        cc.assert_has_teeth(want, what=(N, a, b))
+        cc.compare(host_long(ctrl, draws, N, a, b, h0d=h0), want, (N, a, b, h0 is not None))
+    assert host_long.general_calls(N) == g0
+
+
+@pytest.mark.parametrize("N", [17, 20, 24])
+def test_long_chain_core_degenerate_halves(host_long, N):
+    """Mirror-symmetric controller, chain cut in the middle (both sides of the middle site at odd N), mirror-symmetric
+    draws: the two halves have the same spectrum and the eigenvalue-only weights cannot serve the sample.  Every such
+    sample goes to the general routine (the kernel's LDS routine at N >= 17) and agrees with the oracle for pairs INSIDE
+    one half, where the answer is not 0."""
+    import chain_checks as cc
+    rng = np.random.default_rng(9 + N)
+    C, K, cut = 3, 40, N // 2
+    ctrl = cc.deloc_ctrl(rng, C, N, 0.5)
+    ctrl[:, N] = rng.uniform(0.3 * N, 0.5 * N, C)
+    ctrl[:, N - cut:N] = ctrl[:, :cut][:, ::-1]
+    draws = 0.05 * rng.standard_normal((C, K, N, 3))
+    draws[:, ::5, :, 0] = 0.0
+    for c in range(cut, N - cut + 1):                  # the cut(s)
+        draws[:, ::5, c, 1] = -1.0
+        draws[:, ::5, c, 2] = 0.0
+    for i in range(1, cut):
+        draws[:, ::5, N - i, 1:] = draws[:, ::5, i, 1:]
+    for (a, b) in ((0, cut - 1), (1, 1), (N - 1, N - cut)):
+        g0 = host_long.general_calls(N)
+        got = host_long(ctrl, draws, N, a, b)
+        assert host_long.general_calls(N) - g0 == C * K // 5, (N, a, b)
+        want = orc.fidelity_eigh(ctrl, draws, N, a, b)
+        cc.assert_has_teeth(want[:, ::5], what=(N, a, b))
+        cc.compare(got, want, (N, a, b))
