@@ -135,10 +135,10 @@ def chain_kernels(N):
 # ------------------------------------------------------------------------------------------------------------------------
 
 
-def oracle_pairs(ctrl, draws, N, pairs, h0_diag=None):
+def oracle_pairs(ctrl, draws, N, pairs, h0_diag=None, ring=False):
     """`orc.fidelity_eigh` for several (in, out) pairs of one workload: one eigendecomposition (the oracle's cost) for all"""
     ctrl = np.asarray(ctrl, dtype=np.float64)
-    H = orc.assemble_hamiltonians(np.nan_to_num(ctrl), draws, N, h0_diag)
+    H = orc.assemble_hamiltonians(np.nan_to_num(ctrl), draws, N, h0_diag, ring=ring)
     lam, V = np.linalg.eigh(H)
     phase = np.exp(-1j * np.abs(np.nan_to_num(ctrl[:, N]))[:, None, None] * lam)
     res = {}

@@ -244,3 +244,36 @@ def test_directional_perturbation_on_gpu():
         nm2 = noise.directional_perturbation(Nspin=case["Nspin"], inspin=case["inspin"], outspin=case["outspin"],
                                              noise=case["sigma"])
         assert abs(nm2.evaluate_noisy_fidelity(x, ham_noisy=True) - case["fid"][0][0]) < TOL
+
+
+# ---- known answers (tests/ring_checks.py) ----
+
+
+@pytest.mark.parametrize("N", list(range(2, 17)))
+def test_complex_field_chain_closed_form(be, N, monkeypatch):
+    """C: the spin-j chain in a complex field g through `mc_fidelity_nonhermitian` (N <= 12: the complex symmetric QL route
+    with the expm pass behind it; above: expm alone), and through the expm kernel alone (RC_NH_EXPM_ONLY=1), from both ends to
+    every site: |Im g| <= 0.5 to 1e-9 of max(1, max_out F) plus 1e-9 relative, Im g >= 0.9 - up to and past the exceptional
+    point g = i, where H is one N x N Jordan block - to 1e-7 of it."""
+    from chain_checks import Worst
+    import ring_checks as rc
+    worst = Worst()
+    monkeypatch.delenv("RC_NH_EXPM_ONLY", raising=False)
+    rc.check_complex_field(be, N, worst, route="csym + expm pass" if N <= 12 else "expm")
+    monkeypatch.setenv("RC_NH_EXPM_ONLY", "1")
+    rc.check_complex_field(be, N, worst, route="expm only")
+    monkeypatch.delenv("RC_NH_EXPM_ONLY", raising=False)
+    print(f"complex field N = {N}: {worst}")
+
+
+@pytest.mark.parametrize("N", list(range(2, 13)))
+def test_directional_entry_known_answers(be, N):
+    """D and delocalised rows through `rc_mc_fidelity_directional_f64_async`: gauge-only samples of the spin-j chain (every
+    direction in every row, whichever class route the partition picks) against the closed form from both ends to every site;
+    delocalised controllers (median F >= 1e-2) against the oracle's per-sample expm for every class of (in, out)."""
+    from chain_checks import Worst
+    import ring_checks as rc
+    worst = Worst()
+    rc.check_directional_gauge(be, N, worst)
+    rc.check_directional_deloc(be, N, worst)
+    print(f"directional N = {N}: {worst}")

@@ -253,3 +253,67 @@ def test_release_stream_wrapper_and_ring_stream_context(be):
     be.release_stream(streams[-1])
     be.release_stream(streams[-1])                                     # nothing left: still fine
     be.release_stream()                                                # the current stream
+
+
+# ---- known answers (tests/ring_checks.py): fidelities of order one, where a wrong kernel cannot hide ----
+
+
+@pytest.mark.parametrize("N", list(range(3, 17)))
+def test_ring_known_answers(be, N):
+    """Every ring kernel (auto, ring_hh, jacobi, expm) from both ends to every site against closed forms: A, the flux ring
+    (non-unit h0_offdiag, every coupling e^{i theta}) at Phi = pi / 2 and Phi = 0; B, a ring with one bond cut exactly (through
+    h0_offdiag, and cancelled by the draws) = the spin-j chain with random phases.  AUTO's repair list: nothing (or next to
+    nothing) at Phi = pi / 2, where every level pair is well apart; every sample at Phi = 0, where the pairs k <-> -k are exact."""
+    from chain_checks import Worst, compare
+    import ring_checks as rc
+    worst = Worst()
+    rc.check_flux_ring(be, N, worst)
+    rc.check_cut_ring(be, N, worst)
+    waves, launches, rows, K = {}, 2, 8, 64                              # 8 x 64 samples: 8 waves of 64 per launch
+    for phi in rc.FLUXES:
+        ctrl, off, draws = rc.flux_ring(N, phi, K=K, rows=rows, seed=N)
+        wants = rc.flux_ring_wants(N, phi, ctrl, K)
+        be.general_path_tiles(reset=True)
+        for (a, b) in ((0, N // 2), (N - 1, 1)):
+            worst.add("auto", compare(be.mc_fidelity(ctrl, draws, N, a, b, h0_offdiag=off, ring=True), wants[a, b],
+                                      (N, phi, a, b, "repair list")))
+        waves[phi] = be.general_path_tiles()
+    print(f"ring N = {N}: {worst}; repaired waves of 64 in {launches} launches of {rows * K // 64}: "
+          f"Phi = pi/2 {waves[np.pi / 2]}, Phi = 0 {waves[0.0]}")
+    assert waves[np.pi / 2] <= launches, waves
+    assert waves[0.0] >= launches * rows * K // 64, waves
+
+
+@pytest.mark.parametrize("N", list(range(3, 17)))
+def test_ring_deloc_vs_oracle(be, N):
+    """Delocalised rings (median F >= 1e-2) against the oracle on every ring kernel: every class of (in, out) both ways, XXZ
+    offsets, a NaN row, ragged K (1, 63, 64, 65, 150), one draw set shared by every controller, the torch entry on a fresh
+    side stream."""
+    from chain_checks import Worst
+    import ring_checks as rc
+    worst = Worst()
+    rc.check_ring_deloc(be, N, worst)
+    print(f"ring N = {N}, delocalised: {worst}")
+
+
+@pytest.mark.parametrize("N", [3, 4, 5, 8, 13, 16])
+def test_flux_ring_through_the_noise_model(N):
+    """`structured_perturbation(topo="ring")` with `HH`'s chain bonds edited to e^{i theta} and zero draws - the product path
+    from `HH` through noise._static_terms (h0_offdiag + imaginary draws) to the ring kernel - equals the flux ring's closed form."""
+    from chain_checks import Worst
+    import ring_checks as rc
+    noise = importlib.import_module("code-robchar_amd.noise")
+    worst = Worst()
+    rc.check_flux_ring_product(noise, N, worst=worst)
+    print(f"ring N = {N}, noise model: {worst}")
+
+
+@pytest.mark.parametrize("N", [3, 4, 7, 12, 13, 16])
+def test_flux_ring_imaginary_diagonal(be, N):
+    """E: the flux ring with a uniform imaginary diagonal through `mc_fidelity_nonhermitian(ring=True)` (the Pade-expm
+    kernel): exp(2 gamma T) times A, from both ends to every site, growing and decaying."""
+    from chain_checks import Worst
+    import ring_checks as rc
+    worst = Worst()
+    rc.check_flux_ring_nh(be, N, worst)
+    print(f"ring N = {N}, imaginary diagonal: {worst}")

@@ -237,12 +237,12 @@ def test_legacy_stream_periods_match_mcsim_consumption(host):
 # ----------------------------------------------------------------------------------------------------------------
 # ring topology: Householder tridiagonalisation + shared QL (hermitian_core.h), on the host
 # ----------------------------------------------------------------------------------------------------------------
-def _ring_host(lib, ctrl, draws, N, a, b, h0d=None, corner=1.0, force_general=False):
+def _ring_host(lib, ctrl, draws, N, a, b, h0d=None, corner=1.0, force_general=False, h0o=None):
     C, K = draws.shape[:2]
     ctrl = np.ascontiguousarray(ctrl, dtype=np.float64)
     draws = np.ascontiguousarray(draws, dtype=np.float64)
     h0d = np.zeros(N) if h0d is None else np.ascontiguousarray(h0d, dtype=np.float64)
-    h0o = np.ones(N - 1)
+    h0o = np.ones(N - 1) if h0o is None else np.ascontiguousarray(h0o, dtype=np.float64)
     res = np.empty((C, K))
     lib.rc_host_ring_fidelity.argtypes = [ctypes.c_int, P, P, P, ctypes.c_double, P, ctypes.c_longlong, ctypes.c_longlong,
                                           ctypes.c_int, ctypes.c_int, P, ctypes.c_int]
@@ -323,6 +323,34 @@ def test_ring_mixed_route_vs_oracle(host, N):
         assert np.abs(_ring_host(lib, ctrl, draws, N, a, b, force_general=2) - want).max() < 1e-11
     if N >= 3:
         assert lib.rc_host_ring_mixed_fallbacks() > before
+
+
+@pytest.mark.parametrize("N", list(range(3, 17)))
+def test_ring_routes_known_answers(host, N):
+    """tests/ring_checks.py's closed forms through all three host ring routes (0: all-fp64, 1: the general routine, 2: the
+    mixed-precision route with its all-fp64 fallback): A, the flux ring (non-unit h0_offdiag, imaginary draws), from both ends to
+    every site; B, a ring with one bond cut exactly (the fold's y = 0 branch) = the spin-j chain, with random phases.  The
+    mixed route hands nothing to its fallback at Phi = pi / 2 (levels well apart) and everything at Phi = 0 (exact pairs)."""
+    import ring_checks as rc
+    from chain_checks import compare
+    lib = ctypes.CDLL(host.lib_path)
+    lib.rc_host_ring_mixed_fallbacks.restype = ctypes.c_longlong
+    for fg in (0, 1, 2):
+        for phi in rc.FLUXES:
+            ctrl, off, draws = rc.flux_ring(N, phi, seed=N)
+            before = lib.rc_host_ring_mixed_fallbacks()
+            for (a, b), want in rc.flux_ring_wants(N, phi, ctrl, draws.shape[1]).items():
+                compare(_ring_host(lib, ctrl, draws, N, a, b, force_general=fg, h0o=off), want, (N, fg, phi, a, b))
+            if fg == 2:
+                fell_back = lib.rc_host_ring_mixed_fallbacks() - before
+                assert fell_back == (0 if phi else 2 * N * draws.shape[0] * draws.shape[1]), (N, phi, fell_back)
+        for cut, phases in rc.CUT_VARIANTS:
+            ctrl, off, draws, pos_ctrl, k, lam = rc.cut_ring(N, cut, phases, seed=N)
+            for ap in (0, N - 1):
+                for bp in range(N):
+                    want = np.repeat(rc.closed_form_fid(N, pos_ctrl, ap, bp, lam=lam)[:, None], draws.shape[1], axis=1)
+                    got = _ring_host(lib, ctrl, draws, N, (k + ap) % N, (k + bp) % N, force_general=fg, h0o=off)
+                    compare(got, want, (N, fg, cut, phases, ap, bp))
 
 
 @pytest.mark.parametrize("N", [5, 7, 8, 10, 12, 13])
@@ -638,6 +666,37 @@ def test_complex_symmetric_ql_route_vs_oracle(host, N):
             tol = 1e-10 * np.maximum(1.0, want)
             assert (np.abs(got - want)[okm] <= tol[okm]).all(), (N, kind, a, b, np.abs(got - want)[okm].max())
     assert total_fb <= 3                                           # the route carries (all but) everything itself
+
+
+@pytest.mark.parametrize("N", list(range(2, 13)))
+def test_complex_symmetric_route_complex_field_closed_form(host, N):
+    """tests/ring_checks.py's spin-j chain in a complex field g (H = lam Jx + g Jz, non-unit h0_offdiag) through the complex
+    symmetric QL route: what the route keeps equals the SL(2, C) closed form, relative to max(1, max_out F); at the exceptional
+    point g = i lam (one N x N Jordan block) it keeps nothing - every sample goes to the expm pass."""
+    import ring_checks as rc
+    lib = ctypes.CDLL(host.lib_path)
+    ctrl, off, draws, imag, g = rc.complex_field_chain(N, K=2)
+    C, K = draws.shape[:2]
+    h0d = np.zeros(N)
+    kept = np.zeros(C, dtype=np.int64)
+    for a in (0, N - 1):
+        wants = np.array([rc.complex_field_fid(N, g, ctrl[:, N], a, b) for b in range(N)])
+        scale = np.maximum(1.0, wants.max(axis=0))[:, None]
+        bound = np.where(g.imag >= 0.9, rc.NH_TOL_EP, rc.NH_TOL)[:, None]
+        for b in range(N):
+            got = np.empty((C, K))
+            fb = ctypes.c_longlong(0)
+            assert lib.rc_host_csym_fidelity(N, ctrl.ctypes.data_as(P), h0d.ctypes.data_as(P), off.ctypes.data_as(P),
+                                             draws.ctypes.data_as(P), imag.ctypes.data_as(P), ctypes.c_longlong(C),
+                                             ctypes.c_longlong(K), a, b, got.ctypes.data_as(P), ctypes.byref(fb)) == 0
+            ok = ~np.isnan(got)
+            assert fb.value == (~ok).sum()
+            kept += ok.sum(axis=1)
+            err = np.abs(got - wants[b][:, None]) / scale
+            assert (err[ok] <= np.broadcast_to(bound, err.shape)[ok]).all(), (N, a, b, err[ok].max())
+    at_ep = g == 1j
+    assert kept[at_ep].sum() == 0, (N, kept[at_ep])
+    assert kept[np.abs(g.imag) <= 0.5].min() == 2 * N * K                # well away from it the route carries every sample
 
 
 @pytest.mark.parametrize("N", [3, 4, 7, 10, 13, 16])
