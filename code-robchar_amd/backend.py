@@ -154,6 +154,76 @@ def mc_fidelity(controllers, draws, nspin: int, inspin: int, outspin: int, h0_di
     return res
 
 
+GRAD_OUTPUTS = ("fid", "grad", "mean")
+
+
+def max_nspin_grad() -> int:
+    """`RC_MAX_NSPIN_GRAD` of include/robchar_hip.h: the longest chain the gradient kernel takes"""
+    return 12
+
+
+def mc_fidelity_grad(controllers, draws, nspin: int, inspin: int, outspin: int, h0_diag=None, h0_offdiag=None,
+                     device=None, want=GRAD_OUTPUTS):
+    """Fidelities and their gradient with respect to the controller rows x = [B_0 .. B_{N-1}, T] (chain topology,
+    N <= `max_nspin_grad()`), in one kernel launch.  Returns a dict with the entries named in `want`:
+
+        "fid"  (C, K)         the fidelities (agree with `mc_fidelity` to rounding, not bit for bit: another eigensolver route)
+        "grad" (C, K, N + 1)  dF/dx_0 .. dF/dx_{N-1}, dF/dx_N = sign(x_N) dF/dT, per sample
+        "mean" (C, N + 2)     (mean F, mean dF/dx_0 .. mean dF/dx_N) over the K samples of each row; deterministic
+
+    Shapes and the NumPy / torch convention as in `mc_fidelity`: NumPy in -> NumPy out (blocking); torch CUDA tensors ->
+    tensors on the same device, enqueued on the current stream; draws of shape (1, K, N, 3) with C > 1 = ONE draw set for
+    every controller (the optimiser-side objective `fidelity_ss_av` and its gradient).  A NaN controller row gives NaN."""
+    _check_geometry(nspin, inspin, outspin)
+    want = tuple(want)
+    if not want or any(w not in GRAD_OUTPUTS for w in want):
+        raise ValueError(f"want: a non-empty subset of {GRAD_OUTPUTS}, got {want}")
+    lib = _lib.load()
+    _lib.require_gpu()
+    device = device_index(device)
+    h0d = _small(h0_diag, nspin, "h0_diag")
+    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
+    C = int(controllers.shape[0]) if hasattr(controllers, "shape") else len(controllers)
+    if not hasattr(draws, "shape"):
+        draws = np.asarray(draws, dtype=np.float64)
+    shared = int(draws.shape[0]) == 1 and C > 1
+    K = int(draws.shape[1])
+    if tuple(draws.shape) != ((1 if shared else C), K, nspin, 3):
+        raise ValueError(f"draws: expected ({C}, K, {nspin}, 3) or (1, K, {nspin}, 3), got {tuple(draws.shape)}")
+    stride = 0 if shared else K * nspin * 3
+    shapes = {"fid": (C, K), "grad": (C, K, nspin + 1), "mean": (C, nspin + 2)}
+    if _is_torch(draws):
+        import torch
+        if not (draws.is_cuda and draws.dtype == torch.float64 and draws.is_contiguous()):
+            raise ValueError("draws must be a contiguous float64 CUDA tensor")
+        dev = draws.device
+        ctrl = controllers if _is_torch(controllers) else torch.as_tensor(np.asarray(controllers, dtype=np.float64))
+        ctrl = ctrl.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(ctrl.shape) != (C, nspin + 1):
+            raise ValueError(f"controllers: expected ({C}, {nspin + 1}), got {tuple(ctrl.shape)}")
+        res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
+        ptr = {k: (ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in GRAD_OUTPUTS}
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.rc_mc_fidelity_grad_f64_async(
+            dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o),
+            ctypes.c_void_p(ctrl.data_ptr()), ctypes.c_void_p(draws.data_ptr()), stride, C, K, ptr["fid"], ptr["grad"], ptr["mean"]))
+        return res
+    draws = np.ascontiguousarray(draws, dtype=np.float64)
+    ctrl = _np_f64(controllers, (C, nspin + 1), "controllers")
+    res = {k: np.empty(shapes[k], dtype=np.float64) for k in want}
+    _lib.check(lib.rc_mc_fidelity_grad_f64(device, nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), _ptr(ctrl), _ptr(draws), stride, C, K,
+                                           _ptr(res.get("fid")), _ptr(res.get("grad")), _ptr(res.get("mean"))))
+    return res
+
+
+def grad_general_tiles(device=None, reset: bool = False) -> int:
+    """Tiles of the gradient kernel in which some sample took the textbook per-sample QL since the last reset (diagnostic)."""
+    n = int(_lib.load().rc_stats_grad_general_tiles(device_index(device), int(bool(reset))))
+    if n < 0:
+        _lib.check(n)
+    return n
+
+
 def reduce_metrics(fid, q_thresholds=Q_THRESHOLDS, dkw_eps: float = 0.0, want_sorted: bool = False,
                    device=None, out=None, overlapped: bool = True):
     """Per-controller reductions of a (C, K) fidelity slab on the GPU.

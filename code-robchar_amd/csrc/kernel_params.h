@@ -32,4 +32,20 @@ struct RingRepairList {
     long long* samples;               // [>= C * K] flat sample indices c * K + k
 };
 
+// fidelity + gradient kernel (k_fidelity_grad.inc.h): FidParams' geometry, three optional outputs
+struct GradParams {
+    const double* ctrl;    // [C][N+1]
+    const double* draws;   // [C][K][N][3]
+    double* fid;           // [C][K] or NULL
+    double* grad;          // [C][K][N+1] or NULL
+    double* part;          // [ntiles][N+2] per-tile sums for the row means, or NULL
+    long long C, K;
+    long long draw_cstride;
+    long long tiles_per_ctrl;
+    long long ntiles;
+    int in, out;
+    int align16;
+    StaticH h0;
+};
+
 }  // namespace rckp

@@ -1,0 +1,58 @@
+// librobchar_hip.so, third translation unit: the fidelity-gradient kernels (k_fidelity_grad.inc.h, N = 2 .. RC_MAX_NSPIN_GRAD),
+// compiled in parallel with robchar_hip.hip and robchar_large.hip (`make -j`).  The host side and the C ABI are in
+// robchar_hip.hip, which reaches the launches below through hidden entry points.
+#include <hip/hip_runtime.h>
+
+#include <math.h>
+#include <stdint.h>
+
+#include "../../include/robchar_hip.h"
+#include "kernel_params.h"
+#include "grad_core.h"
+
+namespace {
+
+using rckp::GradParams;
+typedef __attribute__((address_space(1))) const void* rc_gptr_t;
+typedef __attribute__((address_space(3))) void* rc_lptr_t;
+
+// tiles in which some sample's QL hit the sweep cap and took the textbook routine (diagnostic; rare path only)
+__device__ unsigned long long g_grad_general_tiles = 0;
+
+#include "k_fidelity_grad.inc.h"
+
+}  // namespace
+
+extern "C" {
+
+// Enqueues mc_fid_grad_kernel<N> and - when p.part is set - the second pass of the row means into `mean`.  Returns the
+// hipError_t of the launches.
+__attribute__((visibility("hidden"))) int rc_grad_launch(int N, void* stream, const rckp::GradParams* pp, double* mean) {
+    const GradParams& p = *pp;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)p.ntiles);
+    switch (N) {
+#define RC_GRAD_CASE(n) \
+    case n: hipLaunchKernelGGL(mc_fid_grad_kernel<n>, grid, dim3(64), 0, s, p); break;
+        RC_GRAD_CASE(2) RC_GRAD_CASE(3) RC_GRAD_CASE(4) RC_GRAD_CASE(5) RC_GRAD_CASE(6) RC_GRAD_CASE(7) RC_GRAD_CASE(8)
+        RC_GRAD_CASE(9) RC_GRAD_CASE(10) RC_GRAD_CASE(11) RC_GRAD_CASE(12)
+#undef RC_GRAD_CASE
+        default: return (int)hipErrorInvalidValue;
+    }
+    static_assert(RC_MAX_NSPIN_GRAD == 12, "instantiate mc_fid_grad_kernel for every N up to RC_MAX_NSPIN_GRAD");
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    if (p.part && mean) {
+        hipLaunchKernelGGL(mc_fid_grad_mean_kernel, dim3((unsigned)p.C), dim3(64), 0, s, (const double*)p.part, mean,
+                           p.tiles_per_ctrl, N + 2, p.K);
+        e = hipGetLastError();
+    }
+    return (int)e;
+}
+
+// device address of g_grad_general_tiles
+__attribute__((visibility("hidden"))) int rc_grad_counter_addr(void** addr) {
+    return (int)hipGetSymbolAddress(addr, HIP_SYMBOL(g_grad_general_tiles));
+}
+
+}  // extern "C"

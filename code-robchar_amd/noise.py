@@ -160,6 +160,37 @@ class noise_model_base:
         fid = self.fidelity_fixed_set(controllers, draw_set)
         return 1.0 - _be.reduce_metrics(fid, q_thresholds=(), overlapped=False)["rim1"][0]
 
+    # -- the objective's analytic gradient (qnewton.py:162-212: what the reference's L-BFGS consumes) --------------------
+    def fidelity_grad_from_draws(self, controllers, draws, want=backend.GRAD_OUTPUTS):
+        """`backend.mc_fidelity_grad` for this model: (C, N+1) controllers x (C, K, N, 3) or (1, K, N, 3) draws -> dict of
+        "fid" (C, K), "grad" (C, K, N+1), "mean" (C, N+2).  Chain topology only."""
+        diag, off, ring, imag = self._static_terms()
+        if ring:
+            raise NotImplementedError("the fidelity gradient is implemented for the chain topology only")
+        if imag.any():
+            if backend._is_torch(draws):
+                draws = draws.clone()
+                import torch
+                draws[..., 1:, 2] += torch.as_tensor(imag, device=draws.device)
+            else:
+                draws = np.array(draws, dtype=np.float64)
+                draws[..., 1:, 2] += imag
+        return backend.mc_fidelity_grad(controllers, draws, self.Nspin, self.inspin, self.outspin, h0_diag=diag,
+                                        h0_offdiag=off, device=self.device, want=want)
+
+    def fidelity_ss_av_grad(self, controllers, draw_set, reps=None):
+        """`fidelity_ss_av` and its gradient with respect to every controller entry: (fav (C,), grad (C, N+1)), one kernel
+        launch for all controllers.  `fav` is the gradient kernel's own row mean: it agrees with `fidelity_ss_av` to
+        rounding (another eigensolver route and summation order; both are held to 1e-10), so that value and gradient handed
+        to a line search come from the same evaluation."""
+        ctrl = np.asarray(controllers, dtype=np.float64).reshape(-1, self.Nspin + 1)
+        draw_set = np.asarray(draw_set, dtype=np.float64).reshape(-1, self.Nspin, 3)
+        if reps is not None:
+            draw_set = draw_set[: int(reps)]
+        draws = np.ascontiguousarray(draw_set).reshape(1, -1, self.Nspin, 3)
+        mean = self.fidelity_grad_from_draws(ctrl, draws, want=("mean",))["mean"]
+        return mean[:, 0].copy(), mean[:, 1:].copy()
+
     # -- the scalar API -----------------------------------------------------------------------------------------------
     # Reference-style callers loop `for b in range(K): f += nm.evaluate_noisy_fidelity(cont, ham_noisy=True)`
     # (gen_fig_8_arim_fcall_scaling.py:121-132).  One GPU launch + sync per sample costs what the reference's CPU

@@ -49,13 +49,15 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 6       /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 7       /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
                                   6: + rc_build_flags, rc_philox_fused_pays, rc_reduce_ex_f64_async,
                                      rc_legacy_log_is_host_exact, rc_comm_init / rc_comm_size / rc_comm_destroy /
-                                     rc_mc_metrics_gathered_f64 (all additive) */
+                                     rc_mc_metrics_gathered_f64 (all additive);
+                                  7: + rc_mc_fidelity_grad_f64_async, rc_mc_fidelity_grad_f64, rc_stats_grad_general_tiles,
+                                     RC_MAX_NSPIN_GRAD (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -63,6 +65,10 @@ extern "C" {
 #define RC_MAX_NSPIN_CHAIN 24  /* (round 5) chains of 17 .. 24 spins: the register-resident eigenvalue-only kernel (all-fp64 QL +
                                  * adjugate weights, one wave per SIMD) instead of the LDS kernel: N = 17 at 1.2x the N = 16
                                  * time where the LDS kernel took 6x */
+
+#define RC_MAX_NSPIN_GRAD 12   /* (ABI 7) limit of the fidelity-gradient kernel (chain topology).  Its QL carries eigenvector rows in
+                                 * registers: all N up to N = 9, batches of 6 / 5 / 4 rows in 2 / 3 / 5 passes at N = 10 / 11 / 12; the
+                                 * pass count, not a register limit, is what ends the list here */
 
 #define RC_OK 0
 #define RC_EINVAL (-1)   /* bad argument (N out of range, in/out out of range, NULL pointer, ...) */
@@ -138,6 +144,43 @@ int rc_mc_fidelity_ex_f64_async(int device, void* stream, int kernel, int N, int
                                 const double* h0_diag, const double* h0_offdiag, int ring,
                                 const double* controllers_dev, const double* draws_dev,
                                 long long draws_ctrl_stride, long long C, long long K, double* fid_out_dev);
+
+/* (ABI 7) Fidelity AND its gradient with respect to the controller x = [B_0 .. B_{N-1}, T], chain topology,
+ * N = 2 .. RC_MAX_NSPIN_GRAD (RC_ENOSUP above, with a message; rings are not covered):
+ *     F = |<out| exp(-i |x_N| H) |in>|^2,   H = HH + Z(draws) + diag(x_0 .. x_{N-1}),
+ *     dF/dx_l (l < N) and dF/dx_N = sign(x_N) dF/dT (0 at x_N = 0)
+ * - what the reference's L-BFGS consumes (qnewton.py:162-212) - per sample, and their means over the K samples of a controller
+ * row (the optimiser-side objective `fidelity_ss_av` and its gradient when draws_ctrl_stride = 0: one draw set shared by all
+ * controllers).  One kernel launch (plus a small second pass for the means) instead of the 2 (N + 1) launches of central
+ * differences; accurate to the fidelity's own bar times one factor of T (biases) or ||H|| (time entry).
+ * Outputs, each optional (NULL = not wanted; all three NULL: RC_EINVAL "no output"):
+ *     fid_out  [C][K]        the fidelities.  Computed from the same eigensystem as the gradient (all-fp64 QL with eigenvector
+ *                            rows), NOT by the RC_KERNEL_AUTO route: the two agree to rounding (<= 1e-12 observed; both are held
+ *                            to 1e-10 against the oracle), not bit for bit;
+ *     grad_out [C][K][N+1]   the per-sample gradients;
+ *     mean_out [C][N+2]      (mean F, mean dF/dx_0 .. mean dF/dx_N) over the K samples of the row.  Deterministic: fixed
+ *                            summation order, no atomics - the same inputs give the same bits on every run.
+ * A controller row that contains a NaN gives NaN in all three outputs and reads no draws.  `draws_ctrl_stride` as in
+ * rc_mc_fidelity_ex_f64_async (negative = K*N*3).  Arguments are validated before any HIP call; C = 0 or K = 0: RC_OK, nothing
+ * written.  Enqueue-only: device pointers, launched on `stream`; the per-tile partial sums of the means live in a
+ * stream-ordered allocation (hipMallocAsync / hipFreeAsync on `stream`), so the call never synchronises the device.
+ * Stream capture (hipGraph, torch.cuda.graph): with mean_out = NULL the call enqueues one kernel and nothing else and may be
+ * captured; with mean_out set it allocates during the call - capturing that is untested and not supported. */
+int rc_mc_fidelity_grad_f64_async(int device, void* stream, int N, int in, int out,
+                                  const double* h0_diag, const double* h0_offdiag,
+                                  const double* controllers_dev, const double* draws_dev, long long draws_ctrl_stride,
+                                  long long C, long long K, double* fid_out_dev, double* grad_out_dev, double* mean_out_dev);
+
+/* Blocking form of the above: every array may be a host pointer or a device pointer on `device`, as in rc_mc_fidelity_f64.
+ * `draws` holds C*K*N*3 doubles, or K*N*3 when draws_ctrl_stride = 0. */
+int rc_mc_fidelity_grad_f64(int device, int N, int in, int out,
+                            const double* h0_diag, const double* h0_offdiag,
+                            const double* controllers, const double* draws, long long draws_ctrl_stride,
+                            long long C, long long K, double* fid_out, double* grad_out, double* mean_out);
+
+/* Diagnostic (ABI 7): tiles of the gradient kernel in which some sample's QL hit the sweep cap and took the textbook
+ * per-sample routine since the last reset (never observed). */
+long long rc_stats_grad_general_tiles(int device, int reset);
 
 /* The same fidelities with the COUNTER-BASED draws generated inside the kernel (ABI 5; SURVEY.md 8(d): "in philox mode draws
  * are not read"): sample (c, k), site i, slot s is element  offset + ((c K + k) N + i) 3 + s  of stream `seed` - exactly what

@@ -1,0 +1,71 @@
+#!/usr/bin/env python
+"""Time of the fidelity-gradient kernel next to the fidelity kernel it competes with (central differences through
+`mc_fidelity` cost 2 (N + 1) launches per gradient; the kernel earns its place below N + 1).
+
+HIP events around `--launches` launches after `--warmup`, draw tensors rotated through more than the 256 MiB Infinity
+Cache, N = 5, 7, 10 at 100 x 10 000 on the delocalised controller sets; per-sample output and mean-only output separately.
+
+    python scripts/grad_bench.py [--out profiles/grad_bench.txt]"""
+import argparse
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--launches", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    import torch
+    from conftest import highfid_workload
+    be = importlib.import_module("code-robchar_amd.backend")
+    dev = be.compute_device()
+    C, K = 100, 10000
+    lines = [f"# fidelity + gradient kernel vs fidelity kernel, {C} x {K} samples, sigma = 0.05, {args.launches} launches after "
+             f"{args.warmup}, HIP events, draws rotated past the Infinity Cache",
+             f"# device: {torch.cuda.get_device_name(dev)}",
+             "# N  in out | fidelity us | grad (fid+grad+mean) us  ratio | grad (mean only) us  ratio | N + 1"]
+    for cid in (2, 3, 5):
+        N, a, b, ctrl, h0 = highfid_workload(cid, C=C)
+        nbuf = int(np.ceil(300 * 2 ** 20 / (C * K * N * 24))) + 1
+        gen = torch.Generator(device=dev).manual_seed(cid)
+        bufs = [0.05 * torch.randn((C, K, N, 3), dtype=torch.float64, device=dev, generator=gen) for _ in range(nbuf)]
+        ct = torch.from_numpy(ctrl).to(dev)
+        fid = torch.empty((C, K), dtype=torch.float64, device=dev)
+
+        def timed(fn):
+            for i in range(args.warmup):
+                fn(bufs[i % nbuf])
+            torch.cuda.synchronize(dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(args.launches):
+                fn(bufs[i % nbuf])
+            e1.record()
+            torch.cuda.synchronize(dev)
+            return e0.elapsed_time(e1) * 1e3 / args.launches
+
+        t_f = timed(lambda d: be.mc_fidelity(ct, d, N, a, b, h0_diag=h0, out=fid))
+        t_all = timed(lambda d: be.mc_fidelity_grad(ct, d, N, a, b, h0_diag=h0))
+        t_mean = timed(lambda d: be.mc_fidelity_grad(ct, d, N, a, b, h0_diag=h0, want=("mean",)))
+        lines.append(f"{N:3d} {a:3d} {b:3d} | {t_f:9.1f} | {t_all:9.1f} {t_all / t_f:6.2f} | {t_mean:9.1f} {t_mean / t_f:6.2f} | {N + 1}")
+        del bufs
+    text = "\n".join(lines) + "\n"
+    print(text, end="")
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            fh.write(text)
+
+
+if __name__ == "__main__":
+    main()

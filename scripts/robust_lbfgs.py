@@ -1,0 +1,70 @@
+#!/usr/bin/env python
+"""Robust re-optimisation of a shipped controller on the GPU: L-BFGS-B on 1 - fidelity_ss_av over the training set of
+`randHset_constructor`, value AND analytic gradient from one kernel launch per evaluation
+(`noise_model_base.fidelity_ss_av_grad`) - what the reference's qnewton.py does on the CPU with its block-expm gradient.
+
+    python scripts/robust_lbfgs.py [--row 0] [--sigma 0.05] [--maxiter 30] [--train 1000]
+
+Prints value, gradient norm and launches per iteration; `run()` returns the trace for callers (tests)."""
+import argparse
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def run(row=0, sigma=0.05, maxiter=30, train=1000, pair="0-6", verbose=True):
+    from scipy.optimize import minimize
+    noise = importlib.import_module("code-robchar_amd.noise")
+    z = np.load(os.path.join(ROOT, "tests", "golden", "lbfgs_n7.npz"))
+    x0 = np.array(z["ctrl_" + pair][row], dtype=np.float64)
+    a, b = (int(v) for v in pair.split("-"))
+    nm = noise.structured_perturbation(Nspin=7, inspin=a, outspin=b, noise=sigma)
+    train_set, test_set = nm.randHset_constructor(train_size=train, test_size=10000)
+    launches = [0]
+    trace = []                                      # (objective, |gradient|, launches so far) per accepted iterate
+
+    seen = {}                                       # evaluations so far: the callback looks its iterate up here
+
+    def objective(x):
+        key = np.asarray(x, dtype=np.float64).tobytes()
+        if key not in seen:
+            fav, grad = nm.fidelity_ss_av_grad(np.asarray(x)[None], train_set)
+            launches[0] += 1
+            seen[key] = (1.0 - float(fav[0]), -grad[0])
+        return seen[key]
+
+    def callback(xk):
+        val, g = objective(xk)
+        trace.append((val, float(np.linalg.norm(g)), launches[0]))
+        if verbose:
+            print(f"iter {len(trace):3d}  1 - F = {val:.10f}  |grad| = {trace[-1][1]:.3e}  launches = {launches[0]}")
+
+    start = objective(x0)
+    if verbose:
+        print(f"start     1 - F = {start[0]:.10f}  |grad| = {np.linalg.norm(start[1]):.3e}")
+    res = minimize(objective, x0, jac=True, method="L-BFGS-B", callback=callback, options={"maxiter": maxiter})
+    final = objective(res.x)
+    test_fav, _ = nm.fidelity_ss_av_grad(res.x[None], test_set)
+    out = {"x0": x0, "x": res.x, "start": start[0], "final": final[0], "final_grad": final[1], "trace": trace,
+           "launches": launches[0], "test_final": 1.0 - float(test_fav[0]), "model": nm, "train_set": train_set}
+    if verbose:
+        print(f"final     1 - F = {final[0]:.10f} (train)  {out['test_final']:.10f} (test)  after {launches[0]} launches, "
+              f"{len(trace)} iterations")
+    return out
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--row", type=int, default=0)
+    ap.add_argument("--sigma", type=float, default=0.05)
+    ap.add_argument("--maxiter", type=int, default=30)
+    ap.add_argument("--train", type=int, default=1000)
+    ap.add_argument("--pair", default="0-6", choices=("0-6", "0-3"))
+    args = ap.parse_args()
+    run(args.row, args.sigma, args.maxiter, args.train, args.pair)
