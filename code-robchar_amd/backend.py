@@ -174,12 +174,21 @@ def mc_fidelity_grad(controllers, draws, nspin: int, inspin: int, outspin: int, 
     Shapes and the NumPy / torch convention as in `mc_fidelity`: NumPy in -> NumPy out (blocking); torch CUDA tensors ->
     tensors on the same device, enqueued on the current stream; draws of shape (1, K, N, 3) with C > 1 = ONE draw set for
     every controller (the optimiser-side objective `fidelity_ss_av` and its gradient).  A NaN controller row gives NaN."""
+    return _fidelity_derivatives("grad", GRAD_OUTPUTS, lambda C, K, N: {"fid": (C, K), "grad": (C, K, N + 1), "mean": (C, N + 2)},
+                                 controllers, draws, nspin, inspin, outspin, h0_diag, h0_offdiag, device, want)
+
+
+def _fidelity_derivatives(which, outputs, shapes_of, controllers, draws, nspin, inspin, outspin, h0_diag, h0_offdiag, device, want):
+    """`mc_fidelity_grad` (which = "grad") and `mc_fidelity_sens` ("sens"): the two C entries take the same arguments and differ
+    in the shape of their second and third output."""
     _check_geometry(nspin, inspin, outspin)
     want = tuple(want)
-    if not want or any(w not in GRAD_OUTPUTS for w in want):
-        raise ValueError(f"want: a non-empty subset of {GRAD_OUTPUTS}, got {want}")
+    if not want or any(w not in outputs for w in want):
+        raise ValueError(f"want: a non-empty subset of {outputs}, got {want}")
     lib = _lib.load()
     _lib.require_gpu()
+    entry_async = getattr(lib, f"rc_mc_fidelity_{which}_f64_async")
+    entry = getattr(lib, f"rc_mc_fidelity_{which}_f64")
     device = device_index(device)
     h0d = _small(h0_diag, nspin, "h0_diag")
     h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
@@ -191,7 +200,7 @@ def mc_fidelity_grad(controllers, draws, nspin: int, inspin: int, outspin: int, 
     if tuple(draws.shape) != ((1 if shared else C), K, nspin, 3):
         raise ValueError(f"draws: expected ({C}, K, {nspin}, 3) or (1, K, {nspin}, 3), got {tuple(draws.shape)}")
     stride = 0 if shared else K * nspin * 3
-    shapes = {"fid": (C, K), "grad": (C, K, nspin + 1), "mean": (C, nspin + 2)}
+    shapes = shapes_of(C, K, nspin)
     if _is_torch(draws):
         import torch
         if not (draws.is_cuda and draws.dtype == torch.float64 and draws.is_contiguous()):
@@ -202,23 +211,49 @@ def mc_fidelity_grad(controllers, draws, nspin: int, inspin: int, outspin: int, 
         if tuple(ctrl.shape) != (C, nspin + 1):
             raise ValueError(f"controllers: expected ({C}, {nspin + 1}), got {tuple(ctrl.shape)}")
         res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
-        ptr = {k: (ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in GRAD_OUTPUTS}
+        ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in outputs]
         stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rc_mc_fidelity_grad_f64_async(
-            dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o),
-            ctypes.c_void_p(ctrl.data_ptr()), ctypes.c_void_p(draws.data_ptr()), stride, C, K, ptr["fid"], ptr["grad"], ptr["mean"]))
+        _lib.check(entry_async(dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o),
+                               ctypes.c_void_p(ctrl.data_ptr()), ctypes.c_void_p(draws.data_ptr()), stride, C, K, *ptr))
         return res
     draws = np.ascontiguousarray(draws, dtype=np.float64)
     ctrl = _np_f64(controllers, (C, nspin + 1), "controllers")
     res = {k: np.empty(shapes[k], dtype=np.float64) for k in want}
-    _lib.check(lib.rc_mc_fidelity_grad_f64(device, nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), _ptr(ctrl), _ptr(draws), stride, C, K,
-                                           _ptr(res.get("fid")), _ptr(res.get("grad")), _ptr(res.get("mean"))))
+    _lib.check(entry(device, nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), _ptr(ctrl), _ptr(draws), stride, C, K,
+                     *[_ptr(res.get(k)) for k in outputs]))
     return res
 
 
 def grad_general_tiles(device=None, reset: bool = False) -> int:
     """Tiles of the gradient kernel in which some sample took the textbook per-sample QL since the last reset (diagnostic)."""
     n = int(_lib.load().rc_stats_grad_general_tiles(device_index(device), int(bool(reset))))
+    if n < 0:
+        _lib.check(n)
+    return n
+
+
+SENS_OUTPUTS = ("fid", "sens", "mean")
+
+
+def mc_fidelity_sens(controllers, draws, nspin: int, inspin: int, outspin: int, h0_diag=None, h0_offdiag=None,
+                     device=None, want=SENS_OUTPUTS):
+    """Fidelities and their derivatives with respect to the structured noise - the samples' own draws g (chain topology,
+    N <= `max_nspin_grad()`), in one kernel launch.  Returns a dict with the entries named in `want`:
+
+        "fid"  (C, K)         the fidelities (as in `mc_fidelity_grad`)
+        "sens" (C, K, N, 3)   dF/dg in the draws' layout: [i][0] site energy i, [i][1] / [i][2] real / imaginary part of the coupling
+                              of the sites i - 1 and i; [0][1] = [0][2] = 0.  Exactly 0 for both parts of an exactly cut bond
+        "mean" (C, 3 N + 2)   (mean F, mean rho, the N x 3 mean dF/dg) over the K samples of each row, rho = sum g dF/dg: for draws
+                              g = sigma z the mean rho is dFbar/dln(sigma) at that sigma; deterministic
+
+    Shapes, the NumPy / torch convention, the shared draw set (1, K, N, 3) and NaN rows as in `mc_fidelity_grad`."""
+    return _fidelity_derivatives("sens", SENS_OUTPUTS, lambda C, K, N: {"fid": (C, K), "sens": (C, K, N, 3), "mean": (C, 3 * N + 2)},
+                                 controllers, draws, nspin, inspin, outspin, h0_diag, h0_offdiag, device, want)
+
+
+def sens_general_tiles(device=None, reset: bool = False) -> int:
+    """Tiles of the sensitivity kernel in which some sample took the textbook per-sample QL since the last reset (diagnostic)."""
+    n = int(_lib.load().rc_stats_sens_general_tiles(device_index(device), int(bool(reset))))
     if n < 0:
         _lib.check(n)
     return n

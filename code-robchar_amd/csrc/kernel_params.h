@@ -48,4 +48,20 @@ struct GradParams {
     StaticH h0;
 };
 
+// fidelity + noise-sensitivity kernel (k_fidelity_sens.inc.h): the same geometry, derivatives in the draws' own layout
+struct SensParams {
+    const double* ctrl;    // [C][N+1]
+    const double* draws;   // [C][K][N][3]
+    double* fid;           // [C][K] or NULL
+    double* sens;          // [C][K][N][3] or NULL
+    double* part;          // [ntiles][3N+2] per-tile sums for the row means, or NULL
+    long long C, K;
+    long long draw_cstride;
+    long long tiles_per_ctrl;
+    long long ntiles;
+    int in, out;
+    int align16;
+    StaticH h0;
+};
+
 }  // namespace rckp

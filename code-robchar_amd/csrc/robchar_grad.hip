@@ -1,4 +1,5 @@
-// librobchar_hip.so, third translation unit: the fidelity-gradient kernels (k_fidelity_grad.inc.h, N = 2 .. RC_MAX_NSPIN_GRAD),
+// librobchar_hip.so, third translation unit: the fidelity-gradient kernels (k_fidelity_grad.inc.h, N = 2 .. RC_MAX_NSPIN_GRAD)
+// and the noise-sensitivity kernels (k_fidelity_sens.inc.h, same range),
 // compiled in parallel with robchar_hip.hip and robchar_large.hip (`make -j`).  The host side and the C ABI are in
 // robchar_hip.hip, which reaches the launches below through hidden entry points.
 #include <hip/hip_runtime.h>
@@ -9,17 +10,23 @@
 #include "../../include/robchar_hip.h"
 #include "kernel_params.h"
 #include "grad_core.h"
+#include "sens_core.h"
 
 namespace {
 
 using rckp::GradParams;
+using rckp::SensParams;
 typedef __attribute__((address_space(1))) const void* rc_gptr_t;
 typedef __attribute__((address_space(3))) void* rc_lptr_t;
 
 // tiles in which some sample's QL hit the sweep cap and took the textbook routine (diagnostic; rare path only)
 __device__ unsigned long long g_grad_general_tiles = 0;
 
+// the same for mc_fid_sens_kernel
+__device__ unsigned long long g_sens_general_tiles = 0;
+
 #include "k_fidelity_grad.inc.h"
+#include "k_fidelity_sens.inc.h"
 
 }  // namespace
 
@@ -50,9 +57,36 @@ __attribute__((visibility("hidden"))) int rc_grad_launch(int N, void* stream, co
     return (int)e;
 }
 
+// Enqueues mc_fid_sens_kernel<N> and - when p.part is set - the second pass of the row means into `mean` [C][3N+2].
+__attribute__((visibility("hidden"))) int rc_sens_launch(int N, void* stream, const rckp::SensParams* pp, double* mean) {
+    const SensParams& p = *pp;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)p.ntiles);
+    switch (N) {
+#define RC_SENS_CASE(n) \
+    case n: hipLaunchKernelGGL(mc_fid_sens_kernel<n>, grid, dim3(64), 0, s, p); break;
+        RC_SENS_CASE(2) RC_SENS_CASE(3) RC_SENS_CASE(4) RC_SENS_CASE(5) RC_SENS_CASE(6) RC_SENS_CASE(7) RC_SENS_CASE(8)
+        RC_SENS_CASE(9) RC_SENS_CASE(10) RC_SENS_CASE(11) RC_SENS_CASE(12)
+#undef RC_SENS_CASE
+        default: return (int)hipErrorInvalidValue;
+    }
+    static_assert(RC_MAX_NSPIN_GRAD == 12, "instantiate mc_fid_sens_kernel for every N up to RC_MAX_NSPIN_GRAD");
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+    if (p.part && mean) {
+        hipLaunchKernelGGL(mc_fid_grad_mean_kernel, dim3((unsigned)p.C), dim3(64), 0, s, (const double*)p.part, mean,
+                           p.tiles_per_ctrl, 3 * N + 2, p.K);
+        e = hipGetLastError();
+    }
+    return (int)e;
+}
+
 // device address of g_grad_general_tiles
 __attribute__((visibility("hidden"))) int rc_grad_counter_addr(void** addr) {
     return (int)hipGetSymbolAddress(addr, HIP_SYMBOL(g_grad_general_tiles));
+}
+__attribute__((visibility("hidden"))) int rc_sens_counter_addr(void** addr) {
+    return (int)hipGetSymbolAddress(addr, HIP_SYMBOL(g_sens_general_tiles));
 }
 
 }  // extern "C"

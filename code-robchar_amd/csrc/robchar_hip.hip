@@ -61,6 +61,8 @@ __attribute__((visibility("hidden"))) int rc_large_counter_addr(int which, void*
 // third translation unit (robchar_grad.hip): the fidelity-gradient kernels
 __attribute__((visibility("hidden"))) int rc_grad_launch(int N, void* stream, const rckp::GradParams* p, double* mean);
 __attribute__((visibility("hidden"))) int rc_grad_counter_addr(void** addr);
+__attribute__((visibility("hidden"))) int rc_sens_launch(int N, void* stream, const rckp::SensParams* p, double* mean);
+__attribute__((visibility("hidden"))) int rc_sens_counter_addr(void** addr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1470,15 +1472,17 @@ int rc_mc_fidelity_ex_f64_async(int device, void* stream, int kernel, int N, int
 }
 
 // argument checks of the two gradient entries - before any HIP call.  *empty: nothing to do (RC_OK).
+// (`what`, `second`: "fidelity-gradient" / "grad_out", or "noise-sensitivity" / "sens_out" for the two entries further down)
 static int check_grad_args(int N, int in, int out, const void* ctrl, const void* draws, long long* stride, long long C, long long K,
-                           const void* fid, const void* grad, const void* mean, bool* empty) {
+                           const void* fid, const void* grad, const void* mean, bool* empty, const char* what = "fidelity-gradient",
+                           const char* second = "grad_out") {
     *empty = false;
     if (int rc = check_common(N, in, out, C, K)) return rc;
     if (N > RC_MAX_NSPIN_GRAD)
-        return fail(RC_ENOSUP, "the fidelity-gradient kernel supports chains of N <= " + std::to_string(RC_MAX_NSPIN_GRAD) + " spins");
+        return fail(RC_ENOSUP, std::string("the ") + what + " kernel supports chains of N <= " + std::to_string(RC_MAX_NSPIN_GRAD) + " spins");
     if (*stride < 0) *stride = K * N * 3;
     if (*stride != 0 && *stride < K * N * 3) return fail(RC_EINVAL, "draws_ctrl_stride overlaps controllers");
-    if (!fid && !grad && !mean) return fail(RC_EINVAL, "no output requested (fid_out, grad_out and mean_out are all NULL)");
+    if (!fid && !grad && !mean) return fail(RC_EINVAL, std::string("no output requested (fid_out, ") + second + " and mean_out are all NULL)");
     if (C == 0 || K == 0) {
         *empty = true;
         return RC_OK;
@@ -1597,6 +1601,122 @@ long long rc_stats_grad_general_tiles(int device, int reset) {
         return fail(RC_EHIP, "reading the gradient kernel's tile counter failed");
     }
     return (long long)v;
+}
+
+// device pointers; the arguments have been checked
+static int enqueue_sens(hipStream_t s, int N, int in, int out, const double* h0_diag, const double* h0_offdiag, const double* ctrl,
+                        const double* draws, long long draw_cstride, long long C, long long K, double* fid, double* sens,
+                        double* mean) {
+    rckp::SensParams p{};
+    p.ctrl = ctrl;
+    p.draws = draws;
+    p.fid = fid;
+    p.sens = sens;
+    p.part = nullptr;
+    p.C = C;
+    p.K = K;
+    p.draw_cstride = draw_cstride;
+    p.tiles_per_ctrl = (K + 63) / 64;
+    p.ntiles = C * p.tiles_per_ctrl;
+    p.in = in;
+    p.out = out;
+    p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
+    for (int i = 0; i < RC_MAX_NSPIN; ++i) {
+        p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
+        p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
+    }
+    StreamFree part{nullptr, s};                     // per-tile sums of the row means: stream-ordered, released behind the second pass
+    if (mean) {
+        RC_HIP_CHECK(hipMallocAsync(&part.p, (size_t)p.ntiles * (3 * N + 2) * sizeof(double), s));
+        p.part = (double*)part.p;
+    }
+    RC_HIP_CHECK((hipError_t)rc_sens_launch(N, (void*)s, &p, mean));
+    return RC_OK;
+}
+
+int rc_mc_fidelity_sens_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
+                                  const double* controllers_dev, const double* draws_dev, long long draws_ctrl_stride, long long C,
+                                  long long K, double* fid_out_dev, double* sens_out_dev, double* mean_out_dev) {
+    bool empty = false;
+    if (int rc = check_grad_args(N, in, out, controllers_dev, draws_dev, &draws_ctrl_stride, C, K, fid_out_dev, sens_out_dev,
+                                 mean_out_dev, &empty, "noise-sensitivity", "sens_out"))
+        return rc;
+    if (empty) return RC_OK;
+    RC_HIP_CHECK(hipSetDevice(device));
+    return enqueue_sens((hipStream_t)stream, N, in, out, h0_diag, h0_offdiag, controllers_dev, draws_dev, draws_ctrl_stride, C, K,
+                        fid_out_dev, sens_out_dev, mean_out_dev);
+}
+
+int rc_mc_fidelity_sens_f64(int device, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
+                            const double* controllers, const double* draws, long long draws_ctrl_stride, long long C, long long K,
+                            double* fid_out, double* sens_out, double* mean_out) {
+    bool empty = false;
+    if (int rc = check_grad_args(N, in, out, controllers, draws, &draws_ctrl_stride, C, K, fid_out, sens_out, mean_out, &empty,
+                                 "noise-sensitivity", "sens_out"))
+        return rc;
+    if (empty) return RC_OK;
+    if (int rc = device_in_range(device)) return rc;
+    std::lock_guard<std::mutex> lk(g_ctx[device].mu);
+    DeviceCtx* ctx = nullptr;
+    if (int rc = get_ctx(device, &ctx)) return rc;
+    const size_t nb_ctrl = (size_t)C * (N + 1) * sizeof(double);
+    const size_t nb_draw = (draws_ctrl_stride == 0 ? (size_t)K * N * 3 : ((size_t)(C - 1) * draws_ctrl_stride + (size_t)K * N * 3)) *
+                           sizeof(double);
+    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_sens = nb_fid * 3 * N, nb_mean = (size_t)C * (3 * N + 2) * sizeof(double);
+    const bool dc = is_device_ptr(controllers), dd = is_device_ptr(draws);
+    const bool hf = fid_out && !is_device_ptr(fid_out), hs = sens_out && !is_device_ptr(sens_out),
+               hm = mean_out && !is_device_ptr(mean_out);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t need = (dc ? 0 : up(nb_ctrl)) + (dd ? 0 : up(nb_draw)) + (hf ? up(nb_fid) : 0) + (hs ? up(nb_sens) : 0) +
+                        (hm ? up(nb_mean) : 0);
+    if (need) {
+        if (int rc = ensure_ws(ctx, need)) return rc;
+    }
+    char* w = (char*)ctx->ws;
+    const double* d_ctrl = controllers;
+    const double* d_draw = draws;
+    double *d_fid = fid_out, *d_sens = sens_out, *d_mean = mean_out;
+    if (!dc) {
+        RC_HIP_CHECK(hipMemcpyAsync(w, controllers, nb_ctrl, hipMemcpyHostToDevice, ctx->stream));
+        d_ctrl = (const double*)w;
+        w += up(nb_ctrl);
+    }
+    if (!dd) {
+        RC_HIP_CHECK(hipMemcpyAsync(w, draws, nb_draw, hipMemcpyHostToDevice, ctx->stream));
+        d_draw = (const double*)w;
+        w += up(nb_draw);
+    }
+    if (hf) { d_fid = (double*)w; w += up(nb_fid); }
+    if (hs) { d_sens = (double*)w; w += up(nb_sens); }
+    if (hm) { d_mean = (double*)w; w += up(nb_mean); }
+    if (int rc = enqueue_sens(ctx->stream, N, in, out, h0_diag, h0_offdiag, d_ctrl, d_draw, draws_ctrl_stride, C, K, d_fid, d_sens,
+                              d_mean))
+        return rc;
+    if (hf) RC_HIP_CHECK(hipMemcpyAsync(fid_out, d_fid, nb_fid, hipMemcpyDeviceToHost, ctx->stream));
+    if (hs) RC_HIP_CHECK(hipMemcpyAsync(sens_out, d_sens, nb_sens, hipMemcpyDeviceToHost, ctx->stream));
+    if (hm) RC_HIP_CHECK(hipMemcpyAsync(mean_out, d_mean, nb_mean, hipMemcpyDeviceToHost, ctx->stream));
+    RC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return RC_OK;
+}
+
+static long long read_tile_counter(int device, int reset, int (*addr_of)(void**), const char* what) {
+    if (hipSetDevice(device) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RC_EHIP, "hipSetDevice failed");
+    }
+    unsigned long long v = 0;
+    void* addr = nullptr;
+    if (hipDeviceSynchronize() != hipSuccess || addr_of(&addr) != hipSuccess || !addr ||
+        hipMemcpy(&v, addr, sizeof v, hipMemcpyDeviceToHost) != hipSuccess ||
+        (reset && hipMemset(addr, 0, sizeof v) != hipSuccess)) {
+        (void)hipGetLastError();
+        return fail(RC_EHIP, what);
+    }
+    return (long long)v;
+}
+
+long long rc_stats_sens_general_tiles(int device, int reset) {
+    return read_tile_counter(device, reset, rc_sens_counter_addr, "reading the sensitivity kernel's tile counter failed");
 }
 
 int rc_mc_fidelity_philox_f64_async(int device, void* stream, int kernel, int N, int in, int out, const double* h0_diag,

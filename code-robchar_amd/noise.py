@@ -191,6 +191,61 @@ class noise_model_base:
         mean = self.fidelity_grad_from_draws(ctrl, draws, want=("mean",))["mean"]
         return mean[:, 0].copy(), mean[:, 1:].copy()
 
+    # -- differential sensitivity to the structured noise itself ----------------------------------------------------------
+    def fidelity_sens_from_draws(self, controllers, draws, want=backend.SENS_OUTPUTS):
+        """`backend.mc_fidelity_sens` for this model: (C, N+1) controllers x (C, K, N, 3) or (1, K, N, 3) draws -> dict of
+        "fid" (C, K), "sens" (C, K, N, 3) = dF/d(draw), "mean" (C, 3N+2) = (mean F, mean rho, mean dF/d(draw)).  Chain
+        topology only.  rho = sum draw * dF/d(draw) is taken over the DRAWS: the model's static imaginary couplings, which
+        the kernel sees as part of its third draw component, are taken out again (rho is linear in the draws, so
+        rho = rho_kernel - sum_i imag_i dF/dg2_i exactly, and the same for the row means)."""
+        diag, off, ring, imag = self._static_terms()
+        if ring:
+            raise NotImplementedError("the noise sensitivity is implemented for the chain topology only")
+        if imag.any():
+            if backend._is_torch(draws):
+                draws = draws.clone()
+                import torch
+                draws[..., 1:, 2] += torch.as_tensor(imag, device=draws.device)
+            else:
+                draws = np.array(draws, dtype=np.float64)
+                draws[..., 1:, 2] += imag
+        res = backend.mc_fidelity_sens(controllers, draws, self.Nspin, self.inspin, self.outspin, h0_diag=diag,
+                                       h0_offdiag=off, device=self.device, want=want)
+        if imag.any() and "mean" in res:
+            mean = res["mean"]
+            g2 = mean[:, 2:].reshape(mean.shape[0], self.Nspin, 3)[:, 1:, 2]
+            if backend._is_torch(mean):
+                import torch
+                mean[:, 1] -= g2 @ torch.as_tensor(imag, device=mean.device)
+            else:
+                mean[:, 1] -= g2 @ imag
+        return res
+
+    def noise_sensitivity(self, controllers, draws):
+        """What the samples of ONE sigma level say about the neighbourhood of that level, from one kernel launch:
+            "fav"            (C,)       the mean fidelity over the draws (1 - RIM_1),
+            "dfav_dlogsigma" (C,)       its slope along the RIM(sigma) curve: for draws = sigma z, d fav / d ln(sigma) at this sigma,
+            "direction"      (C, N, 3)  the mean derivative per structured direction, in the draws' layout
+                                        ([i][0] site energy i, [i][1] / [i][2] real / imaginary coupling of the sites i - 1, i).
+        `draws`: (C, K, N, 3), or one set (K, N, 3) / (1, K, N, 3) shared by every controller.  NumPy arrays out."""
+        ctrl = np.asarray(controllers, dtype=np.float64).reshape(-1, self.Nspin + 1)
+        if not backend._is_torch(draws):
+            draws = np.ascontiguousarray(draws, dtype=np.float64)
+        if draws.ndim == 3:
+            draws = draws.reshape(1, -1, self.Nspin, 3)
+        mean = self.fidelity_sens_from_draws(ctrl, draws, want=("mean",))["mean"]
+        if backend._is_torch(mean):
+            mean = mean.cpu().numpy()
+        return {"fav": mean[:, 0].copy(), "dfav_dlogsigma": mean[:, 1].copy(),
+                "direction": mean[:, 2:].reshape(-1, self.Nspin, 3).copy()}
+
+    def nominal_sensitivity(self, controllers):
+        """(C, N, 3): dF/d(perturbation) of the unperturbed system per structured direction - the differential sensitivity at
+        sigma = 0.  The imaginary-coupling column is exactly 0 when the static couplings are real (F is even in it)."""
+        ctrl = np.asarray(controllers, dtype=np.float64).reshape(-1, self.Nspin + 1)
+        zero = np.zeros((1, 1, self.Nspin, 3))
+        return self.fidelity_sens_from_draws(ctrl, zero, want=("sens",))["sens"][:, 0].copy()
+
     # -- the scalar API -----------------------------------------------------------------------------------------------
     # Reference-style callers loop `for b in range(K): f += nm.evaluate_noisy_fidelity(cont, ham_noisy=True)`
     # (gen_fig_8_arim_fcall_scaling.py:121-132).  One GPU launch + sync per sample costs what the reference's CPU

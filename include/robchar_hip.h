@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 7       /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 8       /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -57,7 +57,9 @@ extern "C" {
                                      rc_legacy_log_is_host_exact, rc_comm_init / rc_comm_size / rc_comm_destroy /
                                      rc_mc_metrics_gathered_f64 (all additive);
                                   7: + rc_mc_fidelity_grad_f64_async, rc_mc_fidelity_grad_f64, rc_stats_grad_general_tiles,
-                                     RC_MAX_NSPIN_GRAD (additive) */
+                                     RC_MAX_NSPIN_GRAD (additive);
+                                  8: + rc_mc_fidelity_sens_f64_async, rc_mc_fidelity_sens_f64, rc_stats_sens_general_tiles
+                                     (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -181,6 +183,35 @@ int rc_mc_fidelity_grad_f64(int device, int N, int in, int out,
 /* Diagnostic (ABI 7): tiles of the gradient kernel in which some sample's QL hit the sweep cap and took the textbook
  * per-sample routine since the last reset (never observed). */
 long long rc_stats_grad_general_tiles(int device, int reset);
+
+/* (ABI 8) Fidelity AND its derivatives with respect to the structured noise, i.e. the sample's OWN DRAWS, chain topology,
+ * N = 2 .. RC_MAX_NSPIN_GRAD (RC_ENOSUP above; rings are not covered).  With H = HH + Z(g) + diag(x), Z[i][i] = g0_i,
+ * Z[i][i-1] = g1_i + i g2_i (i >= 1), the 3 N - 2 directions are the N site energies, the N - 1 real and the N - 1 imaginary
+ * couplings - the list `directional_perturbation` draws from.  From the eigensystem of the gradient kernel:
+ *     dF/dg0_i = dF/dx_i,    dF/dg1_i = (re_i / r_i) dF/dr_i,    dF/dg2_i = (im_i / r_i) dF/dr_i,
+ * re_i + i im_i the complex coupling of the sites i-1, i and r_i its modulus; both coupling derivatives are exactly 0 at an
+ * exactly cut bond (r_i = 0), which is their true value.  Per sample the radial derivative is rho = sum_{i,c} g_{i,c} dF/dg_{i,c};
+ * for draws g = sigma z its row mean is dFbar/dln(sigma) at that sigma (sigma itself never enters).
+ * Outputs, each optional (NULL = not wanted; all three NULL: RC_EINVAL "no output"):
+ *     fid_out  [C][K]         the fidelities (from the kernel's own eigensystem, as in rc_mc_fidelity_grad_f64_async);
+ *     sens_out [C][K][N][3]   dF/dg in the draws' own layout; the entries [0][1] and [0][2] are 0;
+ *     mean_out [C][3N+2]      (mean F, mean rho, then the N x 3 mean dF/dg) over the K samples of the row.  Deterministic: fixed
+ *                             summation order, no atomics.
+ * NaN rows, `draws_ctrl_stride` (0 = one draw set shared by all controllers), argument checks before any HIP call, empty
+ * batches, the stream-ordered scratch allocation behind mean_out and stream capture: as in rc_mc_fidelity_grad_f64_async. */
+int rc_mc_fidelity_sens_f64_async(int device, void* stream, int N, int in, int out,
+                                  const double* h0_diag, const double* h0_offdiag,
+                                  const double* controllers_dev, const double* draws_dev, long long draws_ctrl_stride,
+                                  long long C, long long K, double* fid_out_dev, double* sens_out_dev, double* mean_out_dev);
+
+/* Blocking form of the above: every array may be a host pointer or a device pointer on `device`. */
+int rc_mc_fidelity_sens_f64(int device, int N, int in, int out,
+                            const double* h0_diag, const double* h0_offdiag,
+                            const double* controllers, const double* draws, long long draws_ctrl_stride,
+                            long long C, long long K, double* fid_out, double* sens_out, double* mean_out);
+
+/* Diagnostic (ABI 8): the counter of rc_stats_grad_general_tiles for the noise-sensitivity kernel. */
+long long rc_stats_sens_general_tiles(int device, int reset);
 
 /* The same fidelities with the COUNTER-BASED draws generated inside the kernel (ABI 5; SURVEY.md 8(d): "in philox mode draws
  * are not read"): sample (c, k), site i, slot s is element  offset + ((c K + k) N + i) 3 + s  of stream `seed` - exactly what
