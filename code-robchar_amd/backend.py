@@ -495,6 +495,54 @@ def mc_fidelity_philox(controllers, n_draws: int, nspin: int, inspin: int, outsp
     return out
 
 
+def mc_fidelity_sens_philox(controllers, n_draws: int, nspin: int, inspin: int, outspin: int, seed: int, offset: int = 0,
+                            sigma=0.05, h0_diag=None, h0_offdiag=None, want=SENS_OUTPUTS):
+    """`mc_fidelity_sens` with the counter-based draws generated INSIDE the kernel (`rc_mc_fidelity_sens_philox_f64_async`):
+    controllers (C, N+1) torch CUDA tensor (a NumPy array is uploaded to the current device) -> dict of torch tensors on that
+    device ("fid" (C, K), "sens" (C, K, N, 3), "mean" (C, 3 N + 2), the entries named in `want`), enqueued on the current stream;
+    bit-identical to
+    `mc_fidelity_sens(controllers, philox_normal((C, K, N, 3), seed, scale=sigma, offset=offset))` without that tensor.
+    `sigma`: a float, or a (C,) tensor / array (one scale per controller row: every sigma level of an algorithm in one launch).
+    The mean rho in "mean"[:, 1] is taken over the generated draws sigma z: d fav / d ln(sigma) at the row's sigma; a
+    row with sigma = 0 gives the nominal sensitivity with rho = 0.  Chain topology, N <= `max_nspin_grad()`."""
+    import torch
+    _check_geometry(nspin, inspin, outspin)
+    want = tuple(want)
+    if not want or any(w not in SENS_OUTPUTS for w in want):
+        raise ValueError(f"want: a non-empty subset of {SENS_OUTPUTS}, got {want}")
+    lib = _lib.load()
+    _lib.require_gpu()
+    if not _is_torch(controllers):                   # (NumPy rows are uploaded to the current device; the results stay there)
+        controllers = torch.from_numpy(np.ascontiguousarray(controllers, dtype=np.float64)).to(compute_device())
+    if not controllers.is_cuda:
+        raise ValueError("controllers must be a torch CUDA tensor (or a NumPy array, which is uploaded)")
+    dev = controllers.device
+    ctrl = controllers.to(dtype=torch.float64).contiguous()
+    C, K = int(ctrl.shape[0]), int(n_draws)
+    if tuple(ctrl.shape) != (C, nspin + 1):
+        raise ValueError(f"controllers: expected ({C}, {nspin + 1})")
+    if K < 0:
+        raise ValueError("n_draws must be non-negative")
+    rows = None
+    if not _is_torch(sigma) and np.ndim(sigma) > 0:
+        sigma = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64))
+    if _is_torch(sigma):
+        rows = sigma.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(rows.shape) != (C,):
+            raise ValueError("sigma: a float or a (C,) tensor")
+    h0d = _small(h0_diag, nspin, "h0_diag")
+    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
+    shapes = {"fid": (C, K), "sens": (C, K, nspin, 3), "mean": (C, 3 * nspin + 2)}
+    res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
+    ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in SENS_OUTPUTS]
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.rc_mc_fidelity_sens_philox_f64_async(dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d),
+                                                        _ptr(h0o), ctypes.c_void_p(ctrl.data_ptr()), int(seed) & (2 ** 64 - 1),
+                                                        int(offset), 0.0 if rows is not None else float(sigma),
+                                                        ctypes.c_void_p(rows.data_ptr()) if rows is not None else None, C, K, *ptr))
+    return res
+
+
 def mc_fidelity_directional(controllers, idx, ab, nspin: int, inspin: int, outspin: int, n_draws: int, h0_diag=None,
                             h0_offdiag=None, out=None):
     """Fidelities of `directional_perturbation` samples straight from (direction index, two normals) per sample

@@ -38,8 +38,9 @@ constexpr int fid_min_waves(int n, int mode) {
 // staging phases: the LDS buffer (64/phases * 3N doubles per wave) must not cap residency below the register limit
 constexpr int fid_phases(int n, int mode) { return n <= 2 ? 1 : (n <= 8 ? 2 : 4); }
 
-// (cos, sin)(2 pi k / 64), k = 0..63: source of the per-wave LDS copy that sincos_table reads
-__device__ const double g_sincos_table[128] = {RC_SINCOS_TABLE_VALUES};
+// (cos, sin)(2 pi k / 64), k = 0..63 - g_sincos_table, the source of the per-wave LDS copy that sincos_table reads - lives in
+// philox_core.inc.h beside the generator that reads it too
+#include "philox_core.inc.h"
 
 // Tiles with at least one sample that left the fast path (sweep cap / degenerate pair) since the last reset: a
 // diagnostic counter, touched only on that rare path (rc_stats_general_tiles).

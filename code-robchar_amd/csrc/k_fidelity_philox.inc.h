@@ -19,16 +19,6 @@ struct PhiloxDraws {
     double sigma;
 };
 
-// element `e` of the stream on its own (rare paths only: one Philox call per element)
-__device__ __forceinline__ double philox_element(unsigned long long seed, unsigned long long e, double scale, const double* lntab,
-                                                 const double* sctab) {
-    double amp, cs, sn;
-    philox_pair(seed, e >> 1, scale, lntab, sctab, amp, cs, sn);
-    double v = (e & 1ull) ? amp * sn : amp * cs;
-    asm volatile("" : "+v"(v));                    // rounded product, never contracted into its consumer (see the kernel)
-    return v;
-}
-
 // (one wave less than the staging kernel where that one sits at its register limit: the pair values live beside the matrix
 // while it is being formed; residency above ~3 waves buys nothing)
 constexpr int fid_philox_min_waves(int n, int mode) {

@@ -64,4 +64,22 @@ struct SensParams {
     StaticH h0;
 };
 
+// fidelity + noise-sensitivity kernel with the counter-based draws generated inside it (k_fidelity_sens_philox.inc.h): SensParams'
+// geometry without a draw tensor; sample (c, k), site i, slot s is element  offset + ((c K + k) N + i) 3 + s  of stream `seed`
+struct SensPhiloxParams {
+    const double* ctrl;    // [C][N+1]
+    double* fid;           // [C][K] or NULL
+    double* sens;          // [C][K][N][3] or NULL
+    double* part;          // [ntiles][3N+2] per-tile sums for the row means, or NULL
+    long long C, K;
+    long long tiles_per_ctrl;
+    long long ntiles;
+    int in, out;
+    unsigned long long seed;
+    unsigned long long offset;        // stream element of sample (c = 0, k = 0), site 0, slot 0
+    const double* sigma_rows;         // [C] scale per controller row, or NULL: `sigma` for all
+    double sigma;
+    StaticH h0;
+};
+
 }  // namespace rckp

@@ -659,6 +659,90 @@ class MCDataSim:
         # the encoder threads and `tolist()` contend for the interpreter lock)
         return {algo: {k: v.tolist() for k, v in tab.items()} for algo, tab in arrays.items()}
 
+    # ------------------------------------------------------------------ differential sensitivity to the noise
+    _SENS_MAX_TILES = 0x7fffffff         # tiles (64 samples of one row) of one kernel launch
+
+    def get_sensitivity_dict(self, training_noise: str = None, noises: np.ndarray = None, algoname=None, samples: int = None,
+                             seed: int = None) -> dict:
+        """The slope of the RIM(sigma) curve and the per-direction sensitivities, per algorithm, sigma level and controller:
+
+            {algo: {"noises": [L], "fav": [L][C], "dfav_dlogsigma": [L][C], "direction": [L][C][N][3]}}     (nested lists)
+
+        `fav` is the mean fidelity 1 - RIM_1 over K = `samples` (default: `bootreps`) draws at the level, `dfav_dlogsigma` its
+        derivative with respect to ln(sigma) there (exactly 0 at sigma = 0), `direction` the mean dF/d(perturbation) per
+        structured direction in the draws' layout ([i][0] site energy i, [i][1] / [i][2] real / imaginary coupling of the sites
+        i - 1, i; at sigma = 0 the nominal sensitivity).  Controllers padded up to `numcontrollers` are NaN.
+
+        The draws are counter-based and generated inside the kernel (`noise_model.noise_sensitivity_philox`), whatever
+        `rng_mode` says: stream `seed` (default: the instance's), and per algorithm ONE launch over the L * C rows - the
+        controller rows tiled L times, one sigma per row (split by level only where that would exceed the launch's tile limit).
+        Level j, controller c, draw k, site i, slot s is stream element ((j C' + c) K + k) 3 N + 3 i + s, C' the number of
+        controllers the algorithm has; the offsets start at 0 for EVERY algorithm: common random numbers across algorithms (the levels
+        of one algorithm have their own elements each).  Neither NumPy's global
+        stream nor the instance's Philox offset is consumed: a later `get_fid_dists` is unaffected.
+
+        Cached as JSON in `get_mcname(...) + "s"` together with `samples` and `seed`; the file is reused only when both match
+        (and not written with cache_format="none").  One GPU: raises NotImplementedError under an initialised process group or
+        with `devices=...`."""
+        if self.devices is not None:
+            raise NotImplementedError("get_sensitivity_dict runs on one GPU (devices=... is not supported)")
+        try:
+            import torch.distributed as dist
+            grouped = dist.is_available() and dist.is_initialized()
+        except ImportError:
+            grouped = False
+        if grouped:
+            raise NotImplementedError("get_sensitivity_dict runs on one GPU (not under an initialised process group)")
+        if isinstance(algoname, str):
+            algos = [algoname]
+        elif algoname is None:
+            algos = list(self.algos)
+        else:
+            algos = list(algoname)
+        if noises is None:
+            noises = self.noises
+        if training_noise is None:
+            training_noise = self.training_noise
+        noises = np.asarray(noises, dtype=np.float64).reshape(-1)
+        K = int(self.bootreps if samples is None else samples)
+        seed = int(self.seed if seed is None else seed)
+        path = self.get_mcname(training_noise, noises) + "s"
+        table = {}
+        if os.path.exists(path):
+            with open(path, "rb") as fh:
+                cached = json.load(fh)
+            if isinstance(cached, dict) and cached.get("samples") == K and cached.get("seed") == seed:
+                table = cached.get("sensitivity", {})
+        missing = [a for a in algos if a not in table]
+        for name in missing:
+            table[name] = self._sensitivity_of_algo(name, noises, training_noise, K, seed)
+        if missing and self.cache_format != "none":
+            with open(path, "w") as fh:
+                json.dump({"samples": K, "seed": seed, "sensitivity": table}, fh)
+        return {name: table[name] for name in algos}
+
+    def _sensitivity_of_algo(self, algoname: str, noises: np.ndarray, training_noise, K: int, seed: int) -> dict:
+        """One algorithm of `get_sensitivity_dict`: NaN-padded (L, C) / (L, C, N, 3) tables as nested lists."""
+        L, C, N = int(noises.size), self.numcontrollers, self.Nspin
+        rows_all = self._controller_rows(algoname, training_noise)
+        nvalid = min(len(rows_all), C)
+        ctrl = np.asarray(rows_all[:nvalid], dtype=np.float64).reshape(nvalid, N + 1)
+        fav = np.full((L, C), np.nan)
+        slope = np.full((L, C), np.nan)
+        direction = np.full((L, C, N, 3), np.nan)
+        if nvalid and K and L:
+            per_level = nvalid * K * N * 3               # stream elements of one level
+            tiles = nvalid * ((K + 63) // 64)
+            step = max(1, min(L, self._SENS_MAX_TILES // tiles))
+            for j0 in range(0, L, step):
+                j1 = min(L, j0 + step)
+                res = self.noise_model.noise_sensitivity_philox(np.tile(ctrl, (j1 - j0, 1)), K, seed,
+                                                                sigma=np.repeat(noises[j0:j1], nvalid), offset=j0 * per_level)
+                fav[j0:j1, :nvalid] = res["fav"].reshape(j1 - j0, nvalid)
+                slope[j0:j1, :nvalid] = res["dfav_dlogsigma"].reshape(j1 - j0, nvalid)
+                direction[j0:j1, :nvalid] = res["direction"].reshape(j1 - j0, nvalid, N, 3)
+        return {"noises": noises.tolist(), "fav": fav.tolist(), "dfav_dlogsigma": slope.tolist(), "direction": direction.tolist()}
+
     # ------------------------------------------------------------------ second caller of the kernel
     _RIMS_CHUNK_DRAWS = 1 << 27          # host draws per batch (1 GiB of fp64)
 

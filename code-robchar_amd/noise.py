@@ -239,6 +239,30 @@ class noise_model_base:
         return {"fav": mean[:, 0].copy(), "dfav_dlogsigma": mean[:, 1].copy(),
                 "direction": mean[:, 2:].reshape(-1, self.Nspin, 3).copy()}
 
+    def noise_sensitivity_philox(self, controllers, n_draws: int, seed: int, sigma=None, offset: int = 0):
+        """`noise_sensitivity` over `n_draws` counter-based draws per controller generated INSIDE the kernel
+        (`backend.mc_fidelity_sens_philox`): no (C, K, N, 3) tensor, the same dict - and the same bits - as
+        `noise_sensitivity(controllers, backend.philox_normal((C, K, N, 3), seed, scale=sigma, offset=offset))`.
+        `sigma`: None = the model's current level; a float; or one value per controller row (array or tensor), so that several
+        levels of one controller set go through one launch.  Row c, draw k, site i, slot s is stream element
+        offset + ((c K + k) N + i) 3 + s.  Chain topology with real static couplings only."""
+        diag, off, ring, imag = self._static_terms()
+        if ring:
+            raise NotImplementedError("the noise sensitivity is implemented for the chain topology only")
+        if imag.any():
+            raise NotImplementedError("draws generated inside the sensitivity kernel: real static couplings only (complex ones: "
+                                      "noise_sensitivity on a draw tensor)")
+        if sigma is None:
+            sigma = float(self.rng.args.get("scale", self.noise))
+        if not backend._is_torch(controllers):
+            controllers = np.asarray(controllers, dtype=np.float64).reshape(-1, self.Nspin + 1)
+        mean = backend.mc_fidelity_sens_philox(controllers, int(n_draws), self.Nspin, self.inspin, self.outspin, seed, offset=offset,
+                                               sigma=sigma, h0_diag=diag, h0_offdiag=off, want=("mean",))["mean"]
+        if backend._is_torch(mean):
+            mean = mean.cpu().numpy()
+        return {"fav": mean[:, 0].copy(), "dfav_dlogsigma": mean[:, 1].copy(),
+                "direction": mean[:, 2:].reshape(-1, self.Nspin, 3).copy()}
+
     def nominal_sensitivity(self, controllers):
         """(C, N, 3): dF/d(perturbation) of the unperturbed system per structured direction - the differential sensitivity at
         sigma = 0.  The imaginary-coupling column is exactly 0 when the static couplings are real (F is even in it)."""

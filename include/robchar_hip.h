@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 8       /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 9       /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -59,7 +59,8 @@ extern "C" {
                                   7: + rc_mc_fidelity_grad_f64_async, rc_mc_fidelity_grad_f64, rc_stats_grad_general_tiles,
                                      RC_MAX_NSPIN_GRAD (additive);
                                   8: + rc_mc_fidelity_sens_f64_async, rc_mc_fidelity_sens_f64, rc_stats_sens_general_tiles
-                                     (additive) */
+                                     (additive);
+                                  9: + rc_mc_fidelity_sens_philox_f64_async (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -227,6 +228,28 @@ int rc_mc_fidelity_philox_f64_async(int device, void* stream, int kernel, int N,
                                     const double* h0_diag, const double* h0_offdiag, const double* controllers_dev,
                                     unsigned long long seed, unsigned long long offset, double sigma,
                                     const double* sigma_rows_dev, long long C, long long K, double* fid_out_dev);
+
+/* (ABI 9) The noise sensitivity of rc_mc_fidelity_sens_f64_async with the COUNTER-BASED draws generated inside the kernel, as
+ * rc_mc_fidelity_philox_f64_async does for the fidelities.  Stream convention: sample (c, k), site i, slot s is element
+ *     offset + ((c K + k) N + i) 3 + s   of stream `seed`,
+ * scaled by `sigma`, or by sigma_rows_dev[c] when that is not NULL (one scale per controller row: all sigma levels of an
+ * algorithm go through ONE launch with the controller rows tiled) - exactly what rc_draws_philox_f64_async(seed, offset, C K N 3,
+ * sigma) would have written, by the same routine.  fid_out, sens_out and mean_out are BIT-IDENTICAL to generating that
+ * [C][K][N][3] tensor and calling rc_mc_fidelity_sens_f64_async on it (same per-sample arithmetic, same summation order of the
+ * row means); only the tensor - 24 N bytes per sample - never exists.
+ * The radial derivative rho = sum g dF/dg is taken over the GENERATED draws g = sigma z, so its row mean in mean_out[c][1] is
+ * dFbar/dln(sigma) at that row's sigma.  A row with sigma = 0 yields the nominal sensitivity (dF/dg of the unperturbed system in
+ * every one of its K samples) with rho = 0 exactly.
+ * Outputs (each optional; all three NULL: RC_EINVAL), NaN rows (NaN everywhere, no draws generated), empty batches (C = 0 or
+ * K = 0: RC_OK, nothing written), argument checks before any HIP call, the stream-ordered scratch allocation behind mean_out and
+ * stream capture: as in rc_mc_fidelity_sens_f64_async.  With sigma_rows_dev = NULL a negative or non-finite `sigma` is RC_EINVAL
+ * (with sigma_rows_dev set, `sigma` is not read).  Chain topology, N = 2 .. RC_MAX_NSPIN_GRAD (RC_ENOSUP above: "N <= 12").
+ * The sweep-cap fallback counts into rc_stats_sens_general_tiles.  Enqueue-only: device pointers, launched on `stream`. */
+int rc_mc_fidelity_sens_philox_f64_async(int device, void* stream, int N, int in, int out,
+                                         const double* h0_diag, const double* h0_offdiag, const double* controllers_dev,
+                                         unsigned long long seed, unsigned long long offset, double sigma,
+                                         const double* sigma_rows_dev, long long C, long long K,
+                                         double* fid_out_dev, double* sens_out_dev, double* mean_out_dev);
 
 /* (ABI 6) 1 when the kernel above is the faster of the two bit-identical routes for this geometry (N <= 13, or N = 14 with
  * {in, out} = {0, N-1}), else 0; 0 everywhere when ROBCHAR_PHILOX_FUSED=0 is in the environment (read per call).  The ONE

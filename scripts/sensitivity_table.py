@@ -4,7 +4,13 @@ and sigma level the RIM_1 (mean infidelity), its slope along the RIM(sigma) curv
 samples, no second Monte-Carlo run - and the structured direction the mean fidelity is most sensitive to; first the nominal
 (sigma = 0) sensitivity.  One `noise_sensitivity` launch per sigma level.
 
-    python scripts/sensitivity_table.py [--pair 0-6] [--rows 8] [--draws 10000]"""
+    python scripts/sensitivity_table.py [--pair 0-6] [--rows 8] [--draws 10000]
+
+`--product`: the table of `MCDataSim.get_sensitivity_dict` instead - per algorithm, sigma level and controller of a controller
+file - with the draws generated inside the kernel, all levels of an algorithm in one launch.  Default: the shipped N = 5
+controller file (the `le` entry of tests/golden/mcsim_run.json); `--le FILE --geometry N,in,out,numcontrollers` takes another.
+
+    python scripts/sensitivity_table.py --product [--samples 10000] [--seed 1] [--training-noise 0.05]"""
 import argparse
 import importlib
 import os
@@ -38,12 +44,61 @@ def run(pair="0-6", rows=8, draws=10000, seed=1, sigmas=SIGMAS):
     return ctrl, out
 
 
+def run_product(le=None, geometry=None, samples=10000, seed=1, training_noise=0.05, noises=(0.0, 0.01, 0.02, 0.05, 0.1)):
+    """`MCDataSim.get_sensitivity_dict` on a controller file, in a scratch experiments directory (no cache file is kept)"""
+    import json
+    import tempfile
+    mcmod = importlib.import_module("code-robchar_amd.mc_data_sim")
+    if le is None:
+        g = json.load(open(os.path.join(ROOT, "tests", "golden", "mcsim_run.json")))
+        ctrl_file, (N, a, b, C) = g["le"], (g["Nspin"], g["inspin"], g["outspin"], g["numcontrollers"])
+    else:
+        ctrl_file, (N, a, b, C) = json.load(open(le)), (int(v) for v in geometry.split(","))
+    cwd = os.getcwd()
+    with tempfile.TemporaryDirectory() as tmp:
+        os.chdir(tmp)
+        try:
+            os.makedirs("experiments/table")
+            json.dump(ctrl_file, open(f"experiments/table/ppo_spin_{N}_{a}-{b}_c_{C}.le", "w"))
+            sim = mcmod.MCDataSim(experiment_name="table", Nspin=N, inspin=a, outspin=b, noises=np.asarray(noises), bootreps=samples,
+                                  training_noise=training_noise, numcontrollers=C, filemarker=".le", verbose=False, seed=seed,
+                                  cache_format="none")
+            return (N, a, b), sim.get_sensitivity_dict()
+        finally:
+            os.chdir(cwd)
+
+
+def print_product(geom, table, samples):
+    print(f"# N = {geom[0]}, transfer {geom[1]}-{geom[2]}, {samples} draws per level generated inside the kernel")
+    for algo, t in table.items():
+        for j, sigma in enumerate(t["noises"]):
+            print(f"# {algo}, sigma = {sigma}:  RIM_1 = 1 - mean F | d RIM_1 / d ln(sigma) | most sensitive direction (mean dF/dg)")
+            for c, fav in enumerate(t["fav"][j]):
+                if fav != fav:                          # a padded controller slot
+                    continue
+                d = np.array(t["direction"][j][c])
+                i, k = np.unravel_index(np.abs(d).argmax(), d.shape)
+                print(f"ctrl {c:2d}  {1.0 - fav:.6f} | {-t['dfav_dlogsigma'][j][c]:+.6f} | {d[i, k]:+.3e}  ({direction_name(i, k)})")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--pair", default="0-6", choices=("0-6", "0-3"))
     ap.add_argument("--rows", type=int, default=8)
     ap.add_argument("--draws", type=int, default=10000)
+    ap.add_argument("--product", action="store_true", help="the table of MCDataSim.get_sensitivity_dict for a controller file")
+    ap.add_argument("--le", default=None, help="controller file (default: the shipped N = 5 one)")
+    ap.add_argument("--geometry", default=None, help="N,in,out,numcontrollers of --le")
+    ap.add_argument("--samples", type=int, default=10000)
+    ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--training-noise", type=float, default=0.05)
     args = ap.parse_args()
+    if args.product:
+        if (args.le is None) != (args.geometry is None):
+            ap.error("--le and --geometry go together")
+        geom, table = run_product(args.le, args.geometry, args.samples, args.seed, args.training_noise)
+        print_product(geom, table, args.samples)
+        return
     ctrl, out = run(args.pair, args.rows, args.draws)
     nom = out["nominal"]
     print(f"# shipped N = 7 L-BFGS controllers, transfer {args.pair}, {args.draws} draws per level")
