@@ -543,6 +543,66 @@ def mc_fidelity_sens_philox(controllers, n_draws: int, nspin: int, inspin: int, 
     return res
 
 
+GRAD_PHILOX_OUTPUTS = ("fid", "grad", "mean", "moment")
+
+
+def mc_fidelity_grad_philox(controllers, n_draws: int, nspin: int, inspin: int, outspin: int, seed: int, offset: int = 0,
+                            sigma=0.05, shared: bool = False, h0_diag=None, h0_offdiag=None, want=GRAD_PHILOX_OUTPUTS):
+    """`mc_fidelity_grad` with the counter-based draws generated INSIDE the kernel (`rc_mc_fidelity_grad_philox_f64_async`), and
+    on request the second-moment sums behind the gradient of the row's variance: controllers (C, N+1) torch CUDA tensor (a NumPy
+    array is uploaded to the current device) -> dict of torch tensors on that device, the entries named in `want`, enqueued on
+    the current stream:
+
+        "fid" (C, K), "grad" (C, K, N+1), "mean" (C, N+2) = (mean F, mean dF/dx)     as `mc_fidelity_grad`,
+        "moment" (C, N+2) = (mean F^2, mean F dF/dx_0 .. mean F dF/dx_N)              (`noise.moments_from_sums`).
+
+    Two draw modes.  shared=False: row c, draw k, site i, slot s is stream element offset + ((c K + k) N + i) 3 + s, and the first
+    three outputs are bit-identical to `mc_fidelity_grad(controllers, philox_normal((C, K, N, 3), seed, scale=sigma, offset=offset))`.
+    shared=True (common random numbers): the element is offset + (k N + i) 3 + s for every row - `mc_fidelity_grad` on the one set
+    `philox_normal((1, K, N, 3), ...)`, bit for bit.  Neither tensor is ever built.
+    `sigma`: a float, or a (C,) tensor / array (one scale per controller row); a row with sigma = 0 gives K identical samples.
+    Chain topology, N <= `max_nspin_grad()`.  No automatic routing: DESIGN.md has the timing against the two-kernel route."""
+    import torch
+    _check_geometry(nspin, inspin, outspin)
+    want = tuple(want)
+    if not want or any(w not in GRAD_PHILOX_OUTPUTS for w in want):
+        raise ValueError(f"want: a non-empty subset of {GRAD_PHILOX_OUTPUTS}, got {want}")
+    if not _is_torch(controllers):
+        controllers = np.ascontiguousarray(controllers, dtype=np.float64)
+    if controllers.ndim != 2 or int(controllers.shape[1]) != nspin + 1:
+        raise ValueError(f"controllers: expected (C, {nspin + 1}), got {tuple(controllers.shape)}")
+    C, K = int(controllers.shape[0]), int(n_draws)
+    if K < 0:
+        raise ValueError("n_draws must be non-negative")
+    if not _is_torch(sigma) and np.ndim(sigma) > 0:
+        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+    if np.ndim(sigma) > 0 and tuple(sigma.shape) != (C,):
+        raise ValueError("sigma: a float or a (C,) tensor")
+    h0d = _small(h0_diag, nspin, "h0_diag")
+    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
+    lib = _lib.load()
+    _lib.require_gpu()
+    if not _is_torch(controllers):                   # (NumPy rows are uploaded to the current device; the results stay there)
+        controllers = torch.from_numpy(controllers).to(compute_device())
+    if not controllers.is_cuda:
+        raise ValueError("controllers must be a torch CUDA tensor (or a NumPy array, which is uploaded)")
+    dev = controllers.device
+    ctrl = controllers.to(dtype=torch.float64).contiguous()
+    rows = None
+    if np.ndim(sigma) > 0:
+        rows = (sigma if _is_torch(sigma) else torch.from_numpy(sigma)).to(device=dev, dtype=torch.float64).contiguous()
+    shapes = {"fid": (C, K), "grad": (C, K, nspin + 1), "mean": (C, nspin + 2), "moment": (C, nspin + 2)}
+    res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
+    ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in GRAD_PHILOX_OUTPUTS]
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.rc_mc_fidelity_grad_philox_f64_async(dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d),
+                                                        _ptr(h0o), ctypes.c_void_p(ctrl.data_ptr()), int(seed) & (2 ** 64 - 1),
+                                                        int(offset), 0.0 if rows is not None else float(sigma),
+                                                        ctypes.c_void_p(rows.data_ptr()) if rows is not None else None,
+                                                        int(bool(shared)), C, K, *ptr))
+    return res
+
+
 def mc_fidelity_directional(controllers, idx, ab, nspin: int, inspin: int, outspin: int, n_draws: int, h0_diag=None,
                             h0_offdiag=None, out=None):
     """Fidelities of `directional_perturbation` samples straight from (direction index, two normals) per sample

@@ -82,4 +82,25 @@ struct SensPhiloxParams {
     StaticH h0;
 };
 
+// fidelity + gradient kernel with the counter-based draws generated inside it (k_fidelity_grad_philox.inc.h): GradParams' geometry
+// without a draw tensor.  Sample (c, k), site i, slot s is element  offset + ((c K + k) N + i) 3 + s  of stream `seed`, or - with
+// `shared` (common random numbers) - element  offset + (k N + i) 3 + s  for every c.
+struct GradPhiloxParams {
+    const double* ctrl;    // [C][N+1]
+    double* fid;           // [C][K] or NULL
+    double* grad;          // [C][K][N+1] or NULL
+    double* part;          // [ntiles][N+2] per-tile sums for the row means ([ntiles][2N+4] with `moments`), or NULL
+    long long C, K;
+    long long tiles_per_ctrl;
+    long long ntiles;
+    int in, out;
+    int shared;                       // 1: one draw set for every controller row
+    int moments;                      // 1: the part rows also carry the sums of F^2 and F dF/dx
+    unsigned long long seed;
+    unsigned long long offset;        // stream element of sample (c = 0, k = 0), site 0, slot 0
+    const double* sigma_rows;         // [C] scale per controller row, or NULL: `sigma` for all
+    double sigma;
+    StaticH h0;
+};
+
 }  // namespace rckp

@@ -60,6 +60,8 @@ __attribute__((visibility("hidden"))) int rc_large_ring_launch(int N, int mixed,
 __attribute__((visibility("hidden"))) int rc_large_counter_addr(int which, void** addr);
 // third translation unit (robchar_grad.hip): the fidelity-gradient kernels
 __attribute__((visibility("hidden"))) int rc_grad_launch(int N, void* stream, const rckp::GradParams* p, double* mean);
+__attribute__((visibility("hidden"))) int rc_grad_philox_launch(int N, void* stream, const rckp::GradPhiloxParams* p, double* mean,
+                                                                double* moment);
 __attribute__((visibility("hidden"))) int rc_grad_counter_addr(void** addr);
 __attribute__((visibility("hidden"))) int rc_sens_launch(int N, void* stream, const rckp::SensParams* p, double* mean);
 __attribute__((visibility("hidden"))) int rc_sens_counter_addr(void** addr);
@@ -1762,6 +1764,54 @@ int rc_mc_fidelity_sens_philox_f64_async(int device, void* stream, int N, int in
         p.part = (double*)part.p;
     }
     RC_HIP_CHECK((hipError_t)rc_sens_philox_launch(N, (void*)s, &p, mean_out_dev));
+    return RC_OK;
+}
+
+int rc_mc_fidelity_grad_philox_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,
+                                         const double* h0_offdiag, const double* controllers_dev, unsigned long long seed,
+                                         unsigned long long offset, double sigma, const double* sigma_rows_dev, int shared_draws,
+                                         long long C, long long K, double* fid_out_dev, double* grad_out_dev, double* mean_out_dev,
+                                         double* moment_out_dev) {
+    if (int rc = check_common(N, in, out, C, K)) return rc;
+    if (N > RC_MAX_NSPIN_GRAD)
+        return fail(RC_ENOSUP, "the fidelity-gradient kernel with draws generated inside it supports chains of N <= " +
+                                   std::to_string(RC_MAX_NSPIN_GRAD) + " spins");
+    if (!fid_out_dev && !grad_out_dev && !mean_out_dev && !moment_out_dev)
+        return fail(RC_EINVAL, "no output requested (fid_out, grad_out, mean_out and moment_out are all NULL)");
+    if (!sigma_rows_dev && !(sigma >= 0.0 && sigma < HUGE_VAL))
+        return fail(RC_EINVAL, "sigma must be finite and non-negative (or give sigma_rows)");
+    if (C == 0 || K == 0) return RC_OK;
+    if (!controllers_dev) return fail(RC_EINVAL, "NULL array pointer");
+    if ((C * ((K + 63) / 64)) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    RC_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    rckp::GradPhiloxParams p{};
+    p.ctrl = controllers_dev;
+    p.fid = fid_out_dev;
+    p.grad = grad_out_dev;
+    p.part = nullptr;
+    p.C = C;
+    p.K = K;
+    p.tiles_per_ctrl = (K + 63) / 64;
+    p.ntiles = C * p.tiles_per_ctrl;
+    p.in = in;
+    p.out = out;
+    p.shared = shared_draws ? 1 : 0;
+    p.moments = moment_out_dev ? 1 : 0;
+    p.seed = seed;
+    p.offset = offset;
+    p.sigma_rows = sigma_rows_dev;
+    p.sigma = sigma;
+    for (int i = 0; i < RC_MAX_NSPIN; ++i) {
+        p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
+        p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
+    }
+    StreamFree part{nullptr, s};                     // per-tile sums of the row means (and moments), as in enqueue_grad
+    if (mean_out_dev || moment_out_dev) {
+        RC_HIP_CHECK(hipMallocAsync(&part.p, (size_t)p.ntiles * (N + 2) * (p.moments ? 2 : 1) * sizeof(double), s));
+        p.part = (double*)part.p;
+    }
+    RC_HIP_CHECK((hipError_t)rc_grad_philox_launch(N, (void*)s, &p, mean_out_dev, moment_out_dev));
     return RC_OK;
 }
 

@@ -43,6 +43,41 @@ class noise_function:
         return flat.reshape(shape)
 
 
+def moments_from_sums(mean, moment):
+    """Mean, variance and standard deviation of the fidelity over a row's samples AND their gradients with respect to the
+    controller, from the two row sums of `backend.mc_fidelity_grad_philox`: `mean` (..., N+2) = (mean F, mean dF/dx) and `moment`
+    (..., N+2) = (mean F^2, mean F dF/dx).  NumPy arrays or torch tensors in, the same kind out:
+
+        "fav"      (...,)      mean F                      "grad_fav" (..., N+1)  mean dF/dx
+        "var"      (...,)      mean F^2 - fav^2            "grad_var" (..., N+1)  2 (mean F dF/dx - fav grad_fav)
+        "std"      (...,)      sqrt(var)                   "grad_std" (..., N+1)  grad_var / (2 std)
+
+    `var` is the ddof = 0 variance - the convention of the `std` metric (np.std) - so that a risk-averse objective
+    1 - fav + lambda std and its gradient come from one launch.
+    At the rounding floor: `var` is a difference of two numbers of size mean F^2 <= 1, each a sum of K rounded terms, so its
+    absolute error is about K eps mean F^2.  Where the computed `var` is at or below 64 * 2^-52 * mean F^2 - the rounding level
+    of the subtraction itself - `var`, `std` and `grad_std` are reported as exactly 0 (not a NaN or a quotient of two rounding
+    errors); a sigma = 0 row, whose K samples are identical, lands there.  Consequence: below sigma ~ 1e-3 the true variance
+    (~ sigma^4 for a controller at a fidelity maximum, ~ sigma^2 elsewhere) is no longer resolved against K eps mean F^2 - form it
+    from the per-sample outputs ("fid", "grad") instead."""
+    if backend._is_torch(mean):
+        import torch as xp
+    else:
+        xp = np
+        mean, moment = np.asarray(mean, dtype=np.float64), np.asarray(moment, dtype=np.float64)
+    fav, grad_fav = mean[..., 0], mean[..., 1:]
+    m2, mfg = moment[..., 0], moment[..., 1:]
+    var = m2 - fav * fav
+    floor = var <= (64.0 * 2.0 ** -52) * m2                     # (False in a NaN row: it stays NaN)
+    zero = xp.zeros_like(var)
+    var = xp.where(floor, zero, var)
+    grad_var = 2.0 * (mfg - fav[..., None] * grad_fav)
+    std = xp.sqrt(var)
+    safe = xp.where(floor, xp.ones_like(std), std)
+    grad_std = xp.where(floor[..., None], xp.zeros_like(grad_var), grad_var / (2.0 * safe)[..., None])
+    return {"fav": fav, "grad_fav": grad_fav, "var": var, "grad_var": grad_var, "std": std, "grad_std": grad_std}
+
+
 class noise_model_base:
     """Same constructor, attributes and methods as the reference class (noise_model.py:50-115)."""
 
@@ -262,6 +297,29 @@ class noise_model_base:
             mean = mean.cpu().numpy()
         return {"fav": mean[:, 0].copy(), "dfav_dlogsigma": mean[:, 1].copy(),
                 "direction": mean[:, 2:].reshape(-1, self.Nspin, 3).copy()}
+
+    def fidelity_moments_philox(self, controllers, n_draws: int, seed: int, sigma=None, offset: int = 0, shared: bool = False):
+        """Mean, variance and standard deviation of the fidelity over `n_draws` counter-based draws per controller generated
+        INSIDE the gradient kernel, with their gradients with respect to the controller: `moments_from_sums` of the "mean" and
+        "moment" rows of ONE `backend.mc_fidelity_grad_philox` launch (no per-sample output, no draw tensor).  NumPy arrays out.
+        `sigma`: None = the model's current level; a float; or one value per controller row.  shared=False: row c, draw k, site
+        i, slot s is stream element offset + ((c K + k) N + i) 3 + s; shared=True (common random numbers: the same draws for
+        every controller, the `fidelity_ss_av` kind of objective): offset + (k N + i) 3 + s.  Chain topology with real static
+        couplings only."""
+        diag, off, ring, imag = self._static_terms()
+        if ring:
+            raise NotImplementedError("the fidelity gradient is implemented for the chain topology only")
+        if imag.any():
+            raise NotImplementedError("draws generated inside the gradient kernel: real static couplings only (complex ones: "
+                                      "fidelity_grad_from_draws on a draw tensor)")
+        if sigma is None:
+            sigma = float(self.rng.args.get("scale", self.noise))
+        if not backend._is_torch(controllers):
+            controllers = np.asarray(controllers, dtype=np.float64).reshape(-1, self.Nspin + 1)
+        res = backend.mc_fidelity_grad_philox(controllers, int(n_draws), self.Nspin, self.inspin, self.outspin, seed, offset=offset,
+                                              sigma=sigma, shared=shared, h0_diag=diag, h0_offdiag=off, want=("mean", "moment"))
+        mean, moment = (v.cpu().numpy() if backend._is_torch(v) else np.asarray(v) for v in (res["mean"], res["moment"]))
+        return {k: v.copy() for k, v in moments_from_sums(mean, moment).items()}
 
     def nominal_sensitivity(self, controllers):
         """(C, N, 3): dF/d(perturbation) of the unperturbed system per structured direction - the differential sensitivity at

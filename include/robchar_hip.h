@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 9       /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 10      /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -60,7 +60,8 @@ extern "C" {
                                      RC_MAX_NSPIN_GRAD (additive);
                                   8: + rc_mc_fidelity_sens_f64_async, rc_mc_fidelity_sens_f64, rc_stats_sens_general_tiles
                                      (additive);
-                                  9: + rc_mc_fidelity_sens_philox_f64_async (additive) */
+                                  9: + rc_mc_fidelity_sens_philox_f64_async (additive);
+                                  10: + rc_mc_fidelity_grad_philox_f64_async (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -250,6 +251,36 @@ int rc_mc_fidelity_sens_philox_f64_async(int device, void* stream, int N, int in
                                          unsigned long long seed, unsigned long long offset, double sigma,
                                          const double* sigma_rows_dev, long long C, long long K,
                                          double* fid_out_dev, double* sens_out_dev, double* mean_out_dev);
+
+/* (ABI 10) The fidelity gradient of rc_mc_fidelity_grad_f64_async with the COUNTER-BASED draws generated inside the kernel, and on
+ * request the second-moment sums from which the gradient of the row's variance follows.  Two stream conventions, chosen by
+ * `shared_draws`:
+ *     shared_draws = 0 (per-controller draws): sample (c, k), site i, slot s is element
+ *         offset + ((c K + k) N + i) 3 + s   of stream `seed`;
+ *     shared_draws != 0 (shared draws, common random numbers - the fidelity_ss_av objective): the element is
+ *         offset + (k N + i) 3 + s,   the same for every c.
+ * In both the scale is `sigma`, or sigma_rows_dev[c] when that is not NULL (one scale per controller row) - by the routine of
+ * rc_draws_philox_f64_async.  fid_out, grad_out and mean_out are BIT-IDENTICAL to the two-kernel route: generating the
+ * [C][K][N][3] tensor (shared draws: the one [K][N][3] set, draws_ctrl_stride = 0) with rc_draws_philox_f64_async(seed, offset, .,
+ * sigma) and calling rc_mc_fidelity_grad_f64_async on it (same per-sample arithmetic, same summation order of the row means);
+ * only the tensor - 24 N bytes per sample - never exists.  A row with sigma = 0 gives K identical samples.
+ * Outputs, each optional (NULL = not wanted; all four NULL: RC_EINVAL "no output"):
+ *     fid_out    [C][K], grad_out [C][K][N+1], mean_out [C][N+2]: as in rc_mc_fidelity_grad_f64_async;
+ *     moment_out [C][N+2]   (mean F^2, mean F dF/dx_0 .. mean F dF/dx_N) over the K samples of the row, every product rounded
+ *                           once, same fixed summation order as mean_out, no atomics: same inputs, same bits.  With mean_out:
+ *                           grad Var F = 2 (mean F dF/dx - mean F mean dF/dx), Var F = mean F^2 - (mean F)^2 (ddof = 0).  With
+ *                           moment_out = NULL the kernel does none of that work.
+ * NaN rows (NaN in every output, no draws generated), empty batches (C = 0 or K = 0: RC_OK, nothing written), argument checks
+ * before any HIP call and the stream-ordered scratch allocation behind mean_out / moment_out: as in
+ * rc_mc_fidelity_sens_philox_f64_async.  With sigma_rows_dev = NULL a negative or non-finite `sigma` is RC_EINVAL (with
+ * sigma_rows_dev set, `sigma` is not read).  Chain topology, N = 2 .. RC_MAX_NSPIN_GRAD (RC_ENOSUP above: "N <= 12").  The
+ * sweep-cap fallback counts into rc_stats_grad_general_tiles.  Enqueue-only: device pointers, launched on `stream`.
+ * Timing against the two-kernel route: DESIGN.md ("Gradient kernel with its own draws"); no automatic routing anywhere. */
+int rc_mc_fidelity_grad_philox_f64_async(int device, void* stream, int N, int in, int out,
+                                         const double* h0_diag, const double* h0_offdiag, const double* controllers_dev,
+                                         unsigned long long seed, unsigned long long offset, double sigma,
+                                         const double* sigma_rows_dev, int shared_draws, long long C, long long K,
+                                         double* fid_out_dev, double* grad_out_dev, double* mean_out_dev, double* moment_out_dev);
 
 /* (ABI 6) 1 when the kernel above is the faster of the two bit-identical routes for this geometry (N <= 13, or N = 14 with
  * {in, out} = {0, N-1}), else 0; 0 everywhere when ROBCHAR_PHILOX_FUSED=0 is in the environment (read per call).  The ONE

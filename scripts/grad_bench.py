@@ -5,7 +5,14 @@
 HIP events around `--launches` launches after `--warmup`, draw tensors rotated through more than the 256 MiB Infinity
 Cache, N = 5, 7, 10 at 100 x 10 000 on the delocalised controller sets; per-sample output and mean-only output separately.
 
-    python scripts/grad_bench.py [--out profiles/grad_bench.txt]"""
+    python scripts/grad_bench.py [--out profiles/grad_bench.txt]
+
+--philox runs ANOTHER leg instead (the output above is unchanged without it): the gradient kernel that generates its own draws
+(`mc_fidelity_grad_philox`) against the two-kernel route it replaces, N = 5, 7, 10, 12 at 100 x 10 000, sigma = 0.05,
+delocalised sets: (a) `philox_normal` + `mc_fidelity_grad`, mean only; (b) the fused kernel, mean only; (c) the fused kernel,
+mean + moment.  The routes alternate in one process, `--launches` launches after `--warmup`, HIP events, `--repeats` repeats.
+
+    python scripts/grad_bench.py --philox [--out profiles/grad_philox_bench.txt]"""
 import argparse
 import importlib
 import os
@@ -19,17 +26,78 @@ for p in (ROOT, os.path.join(ROOT, "tests")):
         sys.path.insert(0, p)
 
 
+def philox_leg(args, be, dev, C, K):
+    import torch
+    import chain_checks as cc
+    from conftest import highfid_workload
+    sigma, seed = 0.05, 7
+    lines = [f"# gradient kernel with its own draws (mc_fidelity_grad_philox) against philox_normal + mc_fidelity_grad, {C} x {K}, "
+             f"sigma = {sigma}, {args.launches} launches after {args.warmup}, routes alternated, {args.repeats} repeats "
+             "(min .. max, us per launch), HIP events",
+             f"# device: {torch.cuda.get_device_name(dev)}",
+             "# N  in out | (a) two kernels, mean us | (b) fused, mean us | (c) fused, mean + moment us | (b)/(a) | (c)/(b) "
+             "(of the minima) | draw tensor not allocated, MB"]
+    work = {w[0]: w for w in (highfid_workload(cid, C=C) for cid in (2, 3, 5))}
+    work[12] = (12, 0, 11, cc.deloc_ctrl(np.random.default_rng(12), C, 12, 0.5), None)
+
+    def timed_calls(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.launches):
+            fn()
+        e1.record()
+        torch.cuda.synchronize(dev)
+        return e0.elapsed_time(e1) * 1e3 / args.launches
+
+    def spread(v):
+        return f"{min(v):9.1f} .. {max(v):9.1f}"
+
+    for N in (5, 7, 10, 12):
+        _, a, b, ctrl, h0 = work[N]
+        ct = torch.from_numpy(ctrl).to(dev)
+        buf = torch.empty((C, K, N, 3), dtype=torch.float64, device=dev)
+
+        def two():
+            be.philox_normal(buf.shape, seed, scale=sigma, out=buf)
+            be.mc_fidelity_grad(ct, buf, N, a, b, h0_diag=h0, want=("mean",))
+
+        ta, tb, tc = [], [], []
+        for _ in range(args.repeats):
+            ta.append(timed_calls(two))
+            tb.append(timed_calls(lambda: be.mc_fidelity_grad_philox(ct, K, N, a, b, seed, sigma=sigma, h0_diag=h0, want=("mean",))))
+            tc.append(timed_calls(lambda: be.mc_fidelity_grad_philox(ct, K, N, a, b, seed, sigma=sigma, h0_diag=h0,
+                                                                     want=("mean", "moment"))))
+        lines.append(f"{N:3d} {a:3d} {b:3d} | {spread(ta)} | {spread(tb)} | {spread(tc)} | {min(tb) / min(ta):5.2f} | "
+                     f"{min(tc) / min(tb):5.2f} | {buf.numel() * 8 / 1e6:8.1f}")
+        print(lines[-1], flush=True)
+        del buf
+    return "\n".join(lines) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--philox", action="store_true", help="the fused-against-two-kernel leg instead of the kernel table")
+    ap.add_argument("--repeats", type=int, default=3)
     args = ap.parse_args()
     import torch
     from conftest import highfid_workload
     be = importlib.import_module("code-robchar_amd.backend")
     dev = be.compute_device()
     C, K = 100, 10000
+    if args.philox:
+        text = philox_leg(args, be, dev, C, K)
+        print(text, end="")
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                fh.write(text)
+        return
     lines = [f"# fidelity + gradient kernel vs fidelity kernel, {C} x {K} samples, sigma = 0.05, {args.launches} launches after "
              f"{args.warmup}, HIP events, draws rotated past the Infinity Cache",
              f"# device: {torch.cuda.get_device_name(dev)}",
