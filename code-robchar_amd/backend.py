@@ -224,12 +224,17 @@ def _fidelity_derivatives(which, outputs, shapes_of, controllers, draws, nspin, 
     return res
 
 
-def grad_general_tiles(device=None, reset: bool = False) -> int:
-    """Tiles of the gradient kernel in which some sample took the textbook per-sample QL since the last reset (diagnostic)."""
-    n = int(_lib.load().rc_stats_grad_general_tiles(device_index(device), int(bool(reset))))
+def _tile_counter(symbol_name, device, reset) -> int:
+    """One of the library's diagnostic tile counters (`rc_stats_*_tiles`), optionally zeroed behind the read."""
+    n = int(getattr(_lib.load(), symbol_name)(device_index(device), int(bool(reset))))
     if n < 0:
         _lib.check(n)
     return n
+
+
+def grad_general_tiles(device=None, reset: bool = False) -> int:
+    """Tiles of the gradient kernel in which some sample took the textbook per-sample QL since the last reset (diagnostic)."""
+    return _tile_counter("rc_stats_grad_general_tiles", device, reset)
 
 
 SENS_OUTPUTS = ("fid", "sens", "mean")
@@ -253,10 +258,7 @@ def mc_fidelity_sens(controllers, draws, nspin: int, inspin: int, outspin: int, 
 
 def sens_general_tiles(device=None, reset: bool = False) -> int:
     """Tiles of the sensitivity kernel in which some sample took the textbook per-sample QL since the last reset (diagnostic)."""
-    n = int(_lib.load().rc_stats_sens_general_tiles(device_index(device), int(bool(reset))))
-    if n < 0:
-        _lib.check(n)
-    return n
+    return _tile_counter("rc_stats_sens_general_tiles", device, reset)
 
 
 def reduce_metrics(fid, q_thresholds=Q_THRESHOLDS, dkw_eps: float = 0.0, want_sorted: bool = False,
@@ -505,68 +507,19 @@ def mc_fidelity_sens_philox(controllers, n_draws: int, nspin: int, inspin: int, 
     `sigma`: a float, or a (C,) tensor / array (one scale per controller row: every sigma level of an algorithm in one launch).
     The mean rho in "mean"[:, 1] is taken over the generated draws sigma z: d fav / d ln(sigma) at the row's sigma; a
     row with sigma = 0 gives the nominal sensitivity with rho = 0.  Chain topology, N <= `max_nspin_grad()`."""
+    return _fidelity_derivatives_philox("sens", SENS_OUTPUTS, lambda C, K, N: {"fid": (C, K), "sens": (C, K, N, 3), "mean": (C, 3 * N + 2)},
+                                        controllers, n_draws, nspin, inspin, outspin, seed, offset, sigma, h0_diag, h0_offdiag, want, ())
+
+
+def _fidelity_derivatives_philox(which, outputs, shapes_of, controllers, n_draws, nspin, inspin, outspin, seed, offset, sigma,
+                                 h0_diag, h0_offdiag, want, extra_args):
+    """`mc_fidelity_sens_philox` (which = "sens") and `mc_fidelity_grad_philox` ("grad"): the two C entries differ in their outputs
+    and in `extra_args`, which the entry takes between `sigma_rows` and `C`.  Everything is validated before the library is loaded."""
     import torch
     _check_geometry(nspin, inspin, outspin)
     want = tuple(want)
-    if not want or any(w not in SENS_OUTPUTS for w in want):
-        raise ValueError(f"want: a non-empty subset of {SENS_OUTPUTS}, got {want}")
-    lib = _lib.load()
-    _lib.require_gpu()
-    if not _is_torch(controllers):                   # (NumPy rows are uploaded to the current device; the results stay there)
-        controllers = torch.from_numpy(np.ascontiguousarray(controllers, dtype=np.float64)).to(compute_device())
-    if not controllers.is_cuda:
-        raise ValueError("controllers must be a torch CUDA tensor (or a NumPy array, which is uploaded)")
-    dev = controllers.device
-    ctrl = controllers.to(dtype=torch.float64).contiguous()
-    C, K = int(ctrl.shape[0]), int(n_draws)
-    if tuple(ctrl.shape) != (C, nspin + 1):
-        raise ValueError(f"controllers: expected ({C}, {nspin + 1})")
-    if K < 0:
-        raise ValueError("n_draws must be non-negative")
-    rows = None
-    if not _is_torch(sigma) and np.ndim(sigma) > 0:
-        sigma = torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64))
-    if _is_torch(sigma):
-        rows = sigma.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(rows.shape) != (C,):
-            raise ValueError("sigma: a float or a (C,) tensor")
-    h0d = _small(h0_diag, nspin, "h0_diag")
-    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
-    shapes = {"fid": (C, K), "sens": (C, K, nspin, 3), "mean": (C, 3 * nspin + 2)}
-    res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
-    ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in SENS_OUTPUTS]
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.rc_mc_fidelity_sens_philox_f64_async(dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d),
-                                                        _ptr(h0o), ctypes.c_void_p(ctrl.data_ptr()), int(seed) & (2 ** 64 - 1),
-                                                        int(offset), 0.0 if rows is not None else float(sigma),
-                                                        ctypes.c_void_p(rows.data_ptr()) if rows is not None else None, C, K, *ptr))
-    return res
-
-
-GRAD_PHILOX_OUTPUTS = ("fid", "grad", "mean", "moment")
-
-
-def mc_fidelity_grad_philox(controllers, n_draws: int, nspin: int, inspin: int, outspin: int, seed: int, offset: int = 0,
-                            sigma=0.05, shared: bool = False, h0_diag=None, h0_offdiag=None, want=GRAD_PHILOX_OUTPUTS):
-    """`mc_fidelity_grad` with the counter-based draws generated INSIDE the kernel (`rc_mc_fidelity_grad_philox_f64_async`), and
-    on request the second-moment sums behind the gradient of the row's variance: controllers (C, N+1) torch CUDA tensor (a NumPy
-    array is uploaded to the current device) -> dict of torch tensors on that device, the entries named in `want`, enqueued on
-    the current stream:
-
-        "fid" (C, K), "grad" (C, K, N+1), "mean" (C, N+2) = (mean F, mean dF/dx)     as `mc_fidelity_grad`,
-        "moment" (C, N+2) = (mean F^2, mean F dF/dx_0 .. mean F dF/dx_N)              (`noise.moments_from_sums`).
-
-    Two draw modes.  shared=False: row c, draw k, site i, slot s is stream element offset + ((c K + k) N + i) 3 + s, and the first
-    three outputs are bit-identical to `mc_fidelity_grad(controllers, philox_normal((C, K, N, 3), seed, scale=sigma, offset=offset))`.
-    shared=True (common random numbers): the element is offset + (k N + i) 3 + s for every row - `mc_fidelity_grad` on the one set
-    `philox_normal((1, K, N, 3), ...)`, bit for bit.  Neither tensor is ever built.
-    `sigma`: a float, or a (C,) tensor / array (one scale per controller row); a row with sigma = 0 gives K identical samples.
-    Chain topology, N <= `max_nspin_grad()`.  No automatic routing: DESIGN.md has the timing against the two-kernel route."""
-    import torch
-    _check_geometry(nspin, inspin, outspin)
-    want = tuple(want)
-    if not want or any(w not in GRAD_PHILOX_OUTPUTS for w in want):
-        raise ValueError(f"want: a non-empty subset of {GRAD_PHILOX_OUTPUTS}, got {want}")
+    if not want or any(w not in outputs for w in want):
+        raise ValueError(f"want: a non-empty subset of {outputs}, got {want}")
     if not _is_torch(controllers):
         controllers = np.ascontiguousarray(controllers, dtype=np.float64)
     if controllers.ndim != 2 or int(controllers.shape[1]) != nspin + 1:
@@ -591,16 +544,40 @@ def mc_fidelity_grad_philox(controllers, n_draws: int, nspin: int, inspin: int, 
     rows = None
     if np.ndim(sigma) > 0:
         rows = (sigma if _is_torch(sigma) else torch.from_numpy(sigma)).to(device=dev, dtype=torch.float64).contiguous()
-    shapes = {"fid": (C, K), "grad": (C, K, nspin + 1), "mean": (C, nspin + 2), "moment": (C, nspin + 2)}
+    shapes = shapes_of(C, K, nspin)
     res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
-    ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in GRAD_PHILOX_OUTPUTS]
+    ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in outputs]
     stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.rc_mc_fidelity_grad_philox_f64_async(dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d),
-                                                        _ptr(h0o), ctypes.c_void_p(ctrl.data_ptr()), int(seed) & (2 ** 64 - 1),
-                                                        int(offset), 0.0 if rows is not None else float(sigma),
-                                                        ctypes.c_void_p(rows.data_ptr()) if rows is not None else None,
-                                                        int(bool(shared)), C, K, *ptr))
+    entry = getattr(lib, f"rc_mc_fidelity_{which}_philox_f64_async")
+    _lib.check(entry(dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o),
+                     ctypes.c_void_p(ctrl.data_ptr()), int(seed) & (2 ** 64 - 1), int(offset), 0.0 if rows is not None else float(sigma),
+                     ctypes.c_void_p(rows.data_ptr()) if rows is not None else None, *extra_args, C, K, *ptr))
     return res
+
+
+GRAD_PHILOX_OUTPUTS = ("fid", "grad", "mean", "moment")
+
+
+def mc_fidelity_grad_philox(controllers, n_draws: int, nspin: int, inspin: int, outspin: int, seed: int, offset: int = 0,
+                            sigma=0.05, shared: bool = False, h0_diag=None, h0_offdiag=None, want=GRAD_PHILOX_OUTPUTS):
+    """`mc_fidelity_grad` with the counter-based draws generated INSIDE the kernel (`rc_mc_fidelity_grad_philox_f64_async`), and
+    on request the second-moment sums behind the gradient of the row's variance: controllers (C, N+1) torch CUDA tensor (a NumPy
+    array is uploaded to the current device) -> dict of torch tensors on that device, the entries named in `want`, enqueued on
+    the current stream:
+
+        "fid" (C, K), "grad" (C, K, N+1), "mean" (C, N+2) = (mean F, mean dF/dx)     as `mc_fidelity_grad`,
+        "moment" (C, N+2) = (mean F^2, mean F dF/dx_0 .. mean F dF/dx_N)              (`noise.moments_from_sums`).
+
+    Two draw modes.  shared=False: row c, draw k, site i, slot s is stream element offset + ((c K + k) N + i) 3 + s, and the first
+    three outputs are bit-identical to `mc_fidelity_grad(controllers, philox_normal((C, K, N, 3), seed, scale=sigma, offset=offset))`.
+    shared=True (common random numbers): the element is offset + (k N + i) 3 + s for every row - `mc_fidelity_grad` on the one set
+    `philox_normal((1, K, N, 3), ...)`, bit for bit.  Neither tensor is ever built.
+    `sigma`: a float, or a (C,) tensor / array (one scale per controller row); a row with sigma = 0 gives K identical samples.
+    Chain topology, N <= `max_nspin_grad()`.  No automatic routing: DESIGN.md has the timing against the two-kernel route."""
+    return _fidelity_derivatives_philox("grad", GRAD_PHILOX_OUTPUTS,
+                                        lambda C, K, N: {"fid": (C, K), "grad": (C, K, N + 1), "mean": (C, N + 2), "moment": (C, N + 2)},
+                                        controllers, n_draws, nspin, inspin, outspin, seed, offset, sigma, h0_diag, h0_offdiag, want,
+                                        (int(bool(shared)),))
 
 
 def mc_fidelity_directional(controllers, idx, ab, nspin: int, inspin: int, outspin: int, n_draws: int, h0_diag=None,
@@ -712,23 +689,15 @@ class ring_stream:
 def general_path_tiles(device=None, reset: bool = False) -> int:
     """Diagnostic: 64-sample tiles that left the chain kernels' fast path since the last reset (0 on healthy
     workloads; each such tile is recomputed by the much slower general per-sample routine)."""
-    lib = _lib.load()
     _lib.require_gpu()
-    v = lib.rc_stats_general_tiles(device_index(device), int(bool(reset)))
-    if v < 0:
-        _lib.check(int(v))
-    return int(v)
+    return _tile_counter("rc_stats_general_tiles", device, reset)
 
 
 def polish_tiles(device=None, reset: bool = False) -> int:
     """Diagnostic: 64-sample tiles of the mixed-precision eigenvalue path that needed more than its one fp64 step since
     the last reset (a close eigenvalue pair somewhere in the tile; the tile keeps stepping, still on the fast path)."""
-    lib = _lib.load()
     _lib.require_gpu()
-    v = lib.rc_stats_polish_tiles(device_index(device), int(bool(reset)))
-    if v < 0:
-        _lib.check(int(v))
-    return int(v)
+    return _tile_counter("rc_stats_polish_tiles", device, reset)
 
 
 def _devices_arg(devices):

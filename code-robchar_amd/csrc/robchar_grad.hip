@@ -37,109 +37,61 @@ __device__ unsigned long long g_sens_general_tiles = 0;
 
 }  // namespace
 
+// Defines  hipError_t NAME(int N, hipStream_t s, const PARAMS& p):  enqueues KERNEL<N>, N = 2 .. RC_MAX_NSPIN_GRAD, one wave per tile.
+static_assert(RC_MAX_NSPIN_GRAD == 12, "RC_LAUNCH_2_TO_12 instantiates every kernel of this unit for every N up to RC_MAX_NSPIN_GRAD");
+#define RC_LAUNCH_CASE(KERNEL, n) \
+    case n: hipLaunchKernelGGL(KERNEL<n>, dim3((unsigned)p.ntiles), dim3(64), 0, s, p); break;
+#define RC_LAUNCH_2_TO_12(NAME, KERNEL, PARAMS)                                                                                    \
+    static hipError_t NAME(int N, hipStream_t s, const PARAMS& p) {                                                               \
+        switch (N) {                                                                                                              \
+            RC_LAUNCH_CASE(KERNEL, 2) RC_LAUNCH_CASE(KERNEL, 3) RC_LAUNCH_CASE(KERNEL, 4) RC_LAUNCH_CASE(KERNEL, 5)               \
+            RC_LAUNCH_CASE(KERNEL, 6) RC_LAUNCH_CASE(KERNEL, 7) RC_LAUNCH_CASE(KERNEL, 8) RC_LAUNCH_CASE(KERNEL, 9)               \
+            RC_LAUNCH_CASE(KERNEL, 10) RC_LAUNCH_CASE(KERNEL, 11) RC_LAUNCH_CASE(KERNEL, 12)                                      \
+            default: return hipErrorInvalidValue;                                                                                 \
+        }                                                                                                                         \
+        return hipGetLastError();                                                                                                 \
+    }
+RC_LAUNCH_2_TO_12(launch_grad, mc_fid_grad_kernel, rckp::GradParams)
+RC_LAUNCH_2_TO_12(launch_sens, mc_fid_sens_kernel, rckp::SensParams)
+RC_LAUNCH_2_TO_12(launch_sens_philox, mc_fid_sens_philox_kernel, rckp::SensPhiloxParams)
+RC_LAUNCH_2_TO_12(launch_grad_philox, mc_fid_grad_philox_kernel, rckp::GradPhiloxParams)
+#undef RC_LAUNCH_2_TO_12
+#undef RC_LAUNCH_CASE
+
+// The second pass behind a launch that went well (`first`): the row means of the `nent` entries of the part rows into `mean`
+// [C][nent], or - `moments`: the part rows carry the moment sums too - into `mean` and / or `moment`.  Nothing without `part`.
+static int launch_row_means(hipError_t first, hipStream_t s, const double* part, double* mean, double* moment, bool moments, int nent,
+                            long long tiles_per_ctrl, long long K, long long C) {
+    if (first != hipSuccess || !part || !(moments || mean)) return (int)first;
+    if (moments)
+        hipLaunchKernelGGL(mc_fid_grad_moment_mean_kernel, dim3((unsigned)C), dim3(64), 0, s, part, mean, moment, tiles_per_ctrl, nent,
+                           K);
+    else
+        hipLaunchKernelGGL(mc_fid_grad_mean_kernel, dim3((unsigned)C), dim3(64), 0, s, part, mean, tiles_per_ctrl, nent, K);
+    return (int)hipGetLastError();
+}
+
 extern "C" {
 
-// Enqueues mc_fid_grad_kernel<N> and - when p.part is set - the second pass of the row means into `mean`.  Returns the
-// hipError_t of the launches.
-__attribute__((visibility("hidden"))) int rc_grad_launch(int N, void* stream, const rckp::GradParams* pp, double* mean) {
-    const GradParams& p = *pp;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)p.ntiles);
-    switch (N) {
-#define RC_GRAD_CASE(n) \
-    case n: hipLaunchKernelGGL(mc_fid_grad_kernel<n>, grid, dim3(64), 0, s, p); break;
-        RC_GRAD_CASE(2) RC_GRAD_CASE(3) RC_GRAD_CASE(4) RC_GRAD_CASE(5) RC_GRAD_CASE(6) RC_GRAD_CASE(7) RC_GRAD_CASE(8)
-        RC_GRAD_CASE(9) RC_GRAD_CASE(10) RC_GRAD_CASE(11) RC_GRAD_CASE(12)
-#undef RC_GRAD_CASE
-        default: return (int)hipErrorInvalidValue;
-    }
-    static_assert(RC_MAX_NSPIN_GRAD == 12, "instantiate mc_fid_grad_kernel for every N up to RC_MAX_NSPIN_GRAD");
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    if (p.part && mean) {
-        hipLaunchKernelGGL(mc_fid_grad_mean_kernel, dim3((unsigned)p.C), dim3(64), 0, s, (const double*)p.part, mean,
-                           p.tiles_per_ctrl, N + 2, p.K);
-        e = hipGetLastError();
-    }
-    return (int)e;
+// Each enqueues its kernel and - when p->part is set - the second pass of the row means: [C][N+2] for the gradients, [C][3N+2] for
+// the sensitivities.  They return the hipError_t of the launches.
+__attribute__((visibility("hidden"))) int rc_grad_launch(int N, void* s, const rckp::GradParams* p, double* mean) {
+    return launch_row_means(launch_grad(N, (hipStream_t)s, *p), (hipStream_t)s, p->part, mean, nullptr, false, N + 2,
+                            p->tiles_per_ctrl, p->K, p->C);
 }
-
-// Enqueues mc_fid_sens_kernel<N> and - when p.part is set - the second pass of the row means into `mean` [C][3N+2].
-__attribute__((visibility("hidden"))) int rc_sens_launch(int N, void* stream, const rckp::SensParams* pp, double* mean) {
-    const SensParams& p = *pp;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)p.ntiles);
-    switch (N) {
-#define RC_SENS_CASE(n) \
-    case n: hipLaunchKernelGGL(mc_fid_sens_kernel<n>, grid, dim3(64), 0, s, p); break;
-        RC_SENS_CASE(2) RC_SENS_CASE(3) RC_SENS_CASE(4) RC_SENS_CASE(5) RC_SENS_CASE(6) RC_SENS_CASE(7) RC_SENS_CASE(8)
-        RC_SENS_CASE(9) RC_SENS_CASE(10) RC_SENS_CASE(11) RC_SENS_CASE(12)
-#undef RC_SENS_CASE
-        default: return (int)hipErrorInvalidValue;
-    }
-    static_assert(RC_MAX_NSPIN_GRAD == 12, "instantiate mc_fid_sens_kernel for every N up to RC_MAX_NSPIN_GRAD");
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    if (p.part && mean) {
-        hipLaunchKernelGGL(mc_fid_grad_mean_kernel, dim3((unsigned)p.C), dim3(64), 0, s, (const double*)p.part, mean,
-                           p.tiles_per_ctrl, 3 * N + 2, p.K);
-        e = hipGetLastError();
-    }
-    return (int)e;
+__attribute__((visibility("hidden"))) int rc_sens_launch(int N, void* s, const rckp::SensParams* p, double* mean) {
+    return launch_row_means(launch_sens(N, (hipStream_t)s, *p), (hipStream_t)s, p->part, mean, nullptr, false, 3 * N + 2,
+                            p->tiles_per_ctrl, p->K, p->C);
 }
-
-// Enqueues mc_fid_sens_philox_kernel<N> and - when p.part is set - the same second pass of the row means.
-__attribute__((visibility("hidden"))) int rc_sens_philox_launch(int N, void* stream, const rckp::SensPhiloxParams* pp, double* mean) {
-    const SensPhiloxParams& p = *pp;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)p.ntiles);
-    switch (N) {
-#define RC_SENS_CASE(n) \
-    case n: hipLaunchKernelGGL(mc_fid_sens_philox_kernel<n>, grid, dim3(64), 0, s, p); break;
-        RC_SENS_CASE(2) RC_SENS_CASE(3) RC_SENS_CASE(4) RC_SENS_CASE(5) RC_SENS_CASE(6) RC_SENS_CASE(7) RC_SENS_CASE(8)
-        RC_SENS_CASE(9) RC_SENS_CASE(10) RC_SENS_CASE(11) RC_SENS_CASE(12)
-#undef RC_SENS_CASE
-        default: return (int)hipErrorInvalidValue;
-    }
-    static_assert(RC_MAX_NSPIN_GRAD == 12, "instantiate mc_fid_sens_philox_kernel for every N up to RC_MAX_NSPIN_GRAD");
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    if (p.part && mean) {
-        hipLaunchKernelGGL(mc_fid_grad_mean_kernel, dim3((unsigned)p.C), dim3(64), 0, s, (const double*)p.part, mean,
-                           p.tiles_per_ctrl, 3 * N + 2, p.K);
-        e = hipGetLastError();
-    }
-    return (int)e;
+__attribute__((visibility("hidden"))) int rc_sens_philox_launch(int N, void* s, const rckp::SensPhiloxParams* p, double* mean) {
+    return launch_row_means(launch_sens_philox(N, (hipStream_t)s, *p), (hipStream_t)s, p->part, mean, nullptr, false, 3 * N + 2,
+                            p->tiles_per_ctrl, p->K, p->C);
 }
-
-// Enqueues mc_fid_grad_philox_kernel<N> and - when p.part is set - the second pass: mc_fid_grad_mean_kernel into `mean` for the
-// row means alone, mc_fid_grad_moment_mean_kernel into `mean` and / or `moment` when the part rows carry the moment sums.
-__attribute__((visibility("hidden"))) int rc_grad_philox_launch(int N, void* stream, const rckp::GradPhiloxParams* pp, double* mean,
+// (p->moments: the part rows also carry the sums of F^2 and F dF/dx, for `moment`)
+__attribute__((visibility("hidden"))) int rc_grad_philox_launch(int N, void* s, const rckp::GradPhiloxParams* p, double* mean,
                                                                 double* moment) {
-    const GradPhiloxParams& p = *pp;
-    hipStream_t s = (hipStream_t)stream;
-    const dim3 grid((unsigned)p.ntiles);
-    switch (N) {
-#define RC_GRAD_CASE(n) \
-    case n: hipLaunchKernelGGL(mc_fid_grad_philox_kernel<n>, grid, dim3(64), 0, s, p); break;
-        RC_GRAD_CASE(2) RC_GRAD_CASE(3) RC_GRAD_CASE(4) RC_GRAD_CASE(5) RC_GRAD_CASE(6) RC_GRAD_CASE(7) RC_GRAD_CASE(8)
-        RC_GRAD_CASE(9) RC_GRAD_CASE(10) RC_GRAD_CASE(11) RC_GRAD_CASE(12)
-#undef RC_GRAD_CASE
-        default: return (int)hipErrorInvalidValue;
-    }
-    static_assert(RC_MAX_NSPIN_GRAD == 12, "instantiate mc_fid_grad_philox_kernel for every N up to RC_MAX_NSPIN_GRAD");
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    if (p.part && p.moments) {
-        hipLaunchKernelGGL(mc_fid_grad_moment_mean_kernel, dim3((unsigned)p.C), dim3(64), 0, s, (const double*)p.part, mean, moment,
-                           p.tiles_per_ctrl, N + 2, p.K);
-        e = hipGetLastError();
-    } else if (p.part && mean) {
-        hipLaunchKernelGGL(mc_fid_grad_mean_kernel, dim3((unsigned)p.C), dim3(64), 0, s, (const double*)p.part, mean,
-                           p.tiles_per_ctrl, N + 2, p.K);
-        e = hipGetLastError();
-    }
-    return (int)e;
+    return launch_row_means(launch_grad_philox(N, (hipStream_t)s, *p), (hipStream_t)s, p->part, mean, moment, p->moments != 0,
+                            N + 2, p->tiles_per_ctrl, p->K, p->C);
 }
 
 // device address of g_grad_general_tiles

@@ -203,6 +203,14 @@ struct StreamFree {
     }
 };
 
+// the static Hamiltonian of a parameter block: the first N diagonal entries (default 0) and N - 1 couplings (default 1), zeros beyond
+void fill_h0(StaticH& h0, int N, const double* h0_diag, const double* h0_offdiag) {
+    for (int i = 0; i < RC_MAX_NSPIN; ++i) {
+        h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
+        h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
+    }
+}
+
 int check_common(int N, int in, int out, long long C, long long K) {
     if (N < 2 || N > RC_MAX_NSPIN) return fail(RC_EINVAL, "N must be in [2, 32]");
     if (in < 0 || in >= N || out < 0 || out >= N) return fail(RC_EINVAL, "in/out spin index out of range");
@@ -267,10 +275,7 @@ int enqueue_expm(hipStream_t s, int N, int in, int out, const double* h0_diag, c
     p.in = in;
     p.out = out;
     p.ring = ring ? 1 : 0;
-    for (int i = 0; i < RC_MAX_NSPIN; ++i) {
-        p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
-        p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
-    }
+    fill_h0(p.h0, N, h0_diag, h0_offdiag);
     const size_t lds = (size_t)kExpmWaves * kExpmBufs * N * N * sizeof(cplx);
     if (int rc = ensure_func_attr(kAttrExpm, (const void*)mc_fid_expm_kernel,
                                   kExpmWaves * kExpmBufs * RC_MAX_NSPIN_FAST * RC_MAX_NSPIN_FAST * (int)sizeof(cplx)))
@@ -327,10 +332,7 @@ int enqueue_fidelity(hipStream_t s, int kernel, int N, int in, int out, const do
         p.in = in;
         p.out = out;
         p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
-        for (int i = 0; i < RC_MAX_NSPIN; ++i) {
-            p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
-            p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
-        }
+        fill_h0(p.h0, N, h0_diag, h0_offdiag);
         if (p.ntiles > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
         const dim3 grid((unsigned)p.ntiles);
         if (mixed_ring) {
@@ -409,10 +411,7 @@ int enqueue_fidelity(hipStream_t s, int kernel, int N, int in, int out, const do
         p.out = out;
         p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
         p.stamps = g_stamps;
-        for (int i = 0; i < RC_MAX_NSPIN; ++i) {
-            p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
-            p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
-        }
+        fill_h0(p.h0, N, h0_diag, h0_offdiag);
         // chains of 17 .. 24 spins (round 5): the register-resident general-adjugate instantiation (one wave per SIMD) for the
         // eigenvalue-only kernels; the rows mode keeps the LDS kernel there (its 4N more doubles of state do not fit)
         if (N > RC_MAX_NSPIN_CHAIN || (N > RC_MAX_NSPIN_FAST && mode == rc::kWeightsRows)) {
@@ -466,10 +465,7 @@ int enqueue_fidelity(hipStream_t s, int kernel, int N, int in, int out, const do
         p.in = in;
         p.out = out;
         p.ring = ring ? 1 : 0;
-        for (int i = 0; i < RC_MAX_NSPIN; ++i) {
-            p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
-            p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
-        }
+        fill_h0(p.h0, N, h0_diag, h0_offdiag);
         const long long total = C * K;
         const int spw = (N <= 8) ? 8 : 4;                       // samples per wave
         long long blocks = (total + kJacWaves * spw - 1) / (kJacWaves * spw);
@@ -1160,10 +1156,7 @@ int enqueue_directional(hipStream_t s, int N, int in, int out, const double* h0_
         p.blk_counts = (unsigned int*)(ws + 2 * nb_list);
         p.counts = (unsigned int*)(ws + 2 * nb_list + nb_blk);
         p.first = done;
-        for (int i = 0; i < RC_MAX_NSPIN; ++i) {
-            p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
-            p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
-        }
+        fill_h0(p.h0, N, h0_diag, h0_offdiag);
         RC_HIP_CHECK(hipMemsetAsync(p.counts, 0, 256, s));
         hipLaunchKernelGGL(dir_class_count_kernel, dim3((unsigned)nblocks), dim3(kDirPartThreads), 0, s, p, N);
         hipLaunchKernelGGL(dir_class_scatter_kernel, dim3((unsigned)nblocks), dim3(kDirPartThreads), 0, s, p, N);
@@ -1365,6 +1358,139 @@ static long long read_tile_counter(int device, int reset, const Sym& symbol, int
     return (long long)sum;
 }
 
+// ------------------------------------------------------------------------------------------------
+// the derivative family (robchar_grad.hip): what its entries share on the host
+// ------------------------------------------------------------------------------------------------
+// Argument checks of the five entries of the derivative family - all before any HIP call.  `what`: the kernel's name in the
+// N > RC_MAX_NSPIN_GRAD refusal; `outs`: the output arguments, of which `any_out` says whether one is set.  `stride` set: the
+// entry takes a draw tensor (its default is filled in); NULL: it generates its draws from `sigma` / `sigma_rows`.
+// *empty: nothing to do (RC_OK).
+static int check_deriv_args(const char* what, const char* outs, int N, int in, int out, const void* ctrl, const void* draws,
+                            long long* stride, double sigma, const void* sigma_rows, long long C, long long K, bool any_out,
+                            bool* empty) {
+    *empty = false;
+    if (int rc = check_common(N, in, out, C, K)) return rc;
+    if (N > RC_MAX_NSPIN_GRAD)
+        return fail(RC_ENOSUP, std::string("the ") + what + (stride ? " kernel" : " kernel with draws generated inside it") +
+                                   " supports chains of N <= " + std::to_string(RC_MAX_NSPIN_GRAD) + " spins");
+    if (stride && *stride < 0) *stride = K * N * 3;
+    if (stride && *stride != 0 && *stride < K * N * 3) return fail(RC_EINVAL, "draws_ctrl_stride overlaps controllers");
+    if (!any_out) return fail(RC_EINVAL, std::string("no output requested (") + outs + " are all NULL)");
+    if (!stride && !sigma_rows && !(sigma >= 0.0 && sigma < HUGE_VAL))
+        return fail(RC_EINVAL, "sigma must be finite and non-negative (or give sigma_rows)");
+    if (C == 0 || K == 0) {
+        *empty = true;
+        return RC_OK;
+    }
+    if (!ctrl || (stride && !draws)) return fail(RC_EINVAL, "NULL array pointer");
+    if ((C * ((K + 63) / 64)) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    return RC_OK;
+}
+static const char kGradOuts[] = "fid_out, grad_out and mean_out", kSensOuts[] = "fid_out, sens_out and mean_out";
+
+// what the four parameter blocks of the family have in common: controllers, fidelity output, tile geometry, static Hamiltonian
+template <typename P>
+static void fill_deriv_params(P& p, int N, int in, int out, const double* h0_diag, const double* h0_offdiag, const double* ctrl,
+                              long long C, long long K, double* fid) {
+    p.ctrl = ctrl;
+    p.fid = fid;
+    p.C = C;
+    p.K = K;
+    p.tiles_per_ctrl = (K + 63) / 64;
+    p.ntiles = C * p.tiles_per_ctrl;
+    p.in = in;
+    p.out = out;
+    fill_h0(p.h0, N, h0_diag, h0_offdiag);
+}
+
+// With `want_part`: p.part = [ntiles][width] per-tile sums for the second pass, stream-ordered and released behind it.  Then
+// `launch()`: the entry `name` of robchar_grad.hip (named in the error text).
+template <typename P, typename Launch>
+static int launch_with_part(hipStream_t s, P& p, bool want_part, int width, const char* name, Launch launch) {
+    StreamFree part{nullptr, s};
+    if (want_part) {
+        RC_HIP_CHECK(hipMallocAsync(&part.p, (size_t)p.ntiles * width * sizeof(double), s));
+        p.part = (double*)part.p;
+    }
+    const hipError_t e = (hipError_t)launch();
+    if (e != hipSuccess) return fail(RC_EHIP, std::string(name) + ": " + hipGetErrorString(e));
+    return RC_OK;
+}
+
+// device pointers; the arguments have been checked
+static int enqueue_grad(hipStream_t s, int N, int in, int out, const double* h0_diag, const double* h0_offdiag, const double* ctrl,
+                        const double* draws, long long draw_cstride, long long C, long long K, double* fid, double* grad,
+                        double* mean) {
+    rckp::GradParams p{};
+    fill_deriv_params(p, N, in, out, h0_diag, h0_offdiag, ctrl, C, K, fid);
+    p.draws = draws;
+    p.draw_cstride = draw_cstride;
+    p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
+    p.grad = grad;
+    return launch_with_part(s, p, mean != nullptr, N + 2, "rc_grad_launch", [&] { return rc_grad_launch(N, (void*)s, &p, mean); });
+}
+static int enqueue_sens(hipStream_t s, int N, int in, int out, const double* h0_diag, const double* h0_offdiag, const double* ctrl,
+                        const double* draws, long long draw_cstride, long long C, long long K, double* fid, double* sens,
+                        double* mean) {
+    rckp::SensParams p{};
+    fill_deriv_params(p, N, in, out, h0_diag, h0_offdiag, ctrl, C, K, fid);
+    p.draws = draws;
+    p.draw_cstride = draw_cstride;
+    p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
+    p.sens = sens;
+    return launch_with_part(s, p, mean != nullptr, 3 * N + 2, "rc_sens_launch",
+                            [&] { return rc_sens_launch(N, (void*)s, &p, mean); });
+}
+
+// The blocking form of enqueue_grad / enqueue_sens (`enqueue`) on the device's own stream: either input and any output may be a
+// host pointer, which is staged through the device's workspace.  `per_sample`, `per_row`: doubles of the second output per sample
+// and of the mean per controller row.  The arguments have been checked.
+static int blocking_deriv(decltype(&enqueue_grad) enqueue, int per_sample, int per_row, int device, int N, int in, int out,
+                          const double* h0_diag, const double* h0_offdiag, const double* controllers, const double* draws,
+                          long long draws_ctrl_stride, long long C, long long K, double* fid_out, double* second_out, double* mean_out) {
+    if (int rc = device_in_range(device)) return rc;
+    std::lock_guard<std::mutex> lk(g_ctx[device].mu);
+    DeviceCtx* ctx = nullptr;
+    if (int rc = get_ctx(device, &ctx)) return rc;
+    const size_t nb_ctrl = (size_t)C * (N + 1) * sizeof(double);
+    const size_t nb_draw = (draws_ctrl_stride == 0 ? (size_t)K * N * 3 : ((size_t)(C - 1) * draws_ctrl_stride + (size_t)K * N * 3)) *
+                           sizeof(double);
+    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_second = nb_fid * per_sample, nb_mean = (size_t)C * per_row * sizeof(double);
+    const bool dc = is_device_ptr(controllers), dd = is_device_ptr(draws);
+    const bool hf = fid_out && !is_device_ptr(fid_out), hs = second_out && !is_device_ptr(second_out),
+               hm = mean_out && !is_device_ptr(mean_out);
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t need = (dc ? 0 : up(nb_ctrl)) + (dd ? 0 : up(nb_draw)) + (hf ? up(nb_fid) : 0) + (hs ? up(nb_second) : 0) +
+                        (hm ? up(nb_mean) : 0);
+    if (need) {
+        if (int rc = ensure_ws(ctx, need)) return rc;
+    }
+    char* w = (char*)ctx->ws;
+    const double* d_ctrl = controllers;
+    const double* d_draw = draws;
+    double *d_fid = fid_out, *d_second = second_out, *d_mean = mean_out;
+    if (!dc) {
+        RC_HIP_CHECK(hipMemcpyAsync(w, controllers, nb_ctrl, hipMemcpyHostToDevice, ctx->stream));
+        d_ctrl = (const double*)w;
+        w += up(nb_ctrl);
+    }
+    if (!dd) {
+        RC_HIP_CHECK(hipMemcpyAsync(w, draws, nb_draw, hipMemcpyHostToDevice, ctx->stream));
+        d_draw = (const double*)w;
+        w += up(nb_draw);
+    }
+    if (hf) { d_fid = (double*)w; w += up(nb_fid); }
+    if (hs) { d_second = (double*)w; w += up(nb_second); }
+    if (hm) { d_mean = (double*)w; w += up(nb_mean); }
+    if (int rc = enqueue(ctx->stream, N, in, out, h0_diag, h0_offdiag, d_ctrl, d_draw, draws_ctrl_stride, C, K, d_fid, d_second, d_mean))
+        return rc;
+    if (hf) RC_HIP_CHECK(hipMemcpyAsync(fid_out, d_fid, nb_fid, hipMemcpyDeviceToHost, ctx->stream));
+    if (hs) RC_HIP_CHECK(hipMemcpyAsync(second_out, d_second, nb_second, hipMemcpyDeviceToHost, ctx->stream));
+    if (hm) RC_HIP_CHECK(hipMemcpyAsync(mean_out, d_mean, nb_mean, hipMemcpyDeviceToHost, ctx->stream));
+    RC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return RC_OK;
+}
+
 extern "C" {
 
 #ifdef RC_STAMPS
@@ -1474,64 +1600,12 @@ int rc_mc_fidelity_ex_f64_async(int device, void* stream, int kernel, int N, int
                             controllers_dev, draws_dev, draws_ctrl_stride, C, K, fid_out_dev);
 }
 
-// argument checks of the two gradient entries - before any HIP call.  *empty: nothing to do (RC_OK).
-// (`what`, `second`: "fidelity-gradient" / "grad_out", or "noise-sensitivity" / "sens_out" for the two entries further down)
-static int check_grad_args(int N, int in, int out, const void* ctrl, const void* draws, long long* stride, long long C, long long K,
-                           const void* fid, const void* grad, const void* mean, bool* empty, const char* what = "fidelity-gradient",
-                           const char* second = "grad_out") {
-    *empty = false;
-    if (int rc = check_common(N, in, out, C, K)) return rc;
-    if (N > RC_MAX_NSPIN_GRAD)
-        return fail(RC_ENOSUP, std::string("the ") + what + " kernel supports chains of N <= " + std::to_string(RC_MAX_NSPIN_GRAD) + " spins");
-    if (*stride < 0) *stride = K * N * 3;
-    if (*stride != 0 && *stride < K * N * 3) return fail(RC_EINVAL, "draws_ctrl_stride overlaps controllers");
-    if (!fid && !grad && !mean) return fail(RC_EINVAL, std::string("no output requested (fid_out, ") + second + " and mean_out are all NULL)");
-    if (C == 0 || K == 0) {
-        *empty = true;
-        return RC_OK;
-    }
-    if (!ctrl || !draws) return fail(RC_EINVAL, "NULL array pointer");
-    if ((C * ((K + 63) / 64)) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
-    return RC_OK;
-}
-
-// device pointers; the arguments have been checked
-static int enqueue_grad(hipStream_t s, int N, int in, int out, const double* h0_diag, const double* h0_offdiag, const double* ctrl,
-                        const double* draws, long long draw_cstride, long long C, long long K, double* fid, double* grad,
-                        double* mean) {
-    rckp::GradParams p{};
-    p.ctrl = ctrl;
-    p.draws = draws;
-    p.fid = fid;
-    p.grad = grad;
-    p.part = nullptr;
-    p.C = C;
-    p.K = K;
-    p.draw_cstride = draw_cstride;
-    p.tiles_per_ctrl = (K + 63) / 64;
-    p.ntiles = C * p.tiles_per_ctrl;
-    p.in = in;
-    p.out = out;
-    p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
-    for (int i = 0; i < RC_MAX_NSPIN; ++i) {
-        p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
-        p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
-    }
-    StreamFree part{nullptr, s};                     // per-tile sums of the row means: stream-ordered, released behind the second pass
-    if (mean) {
-        RC_HIP_CHECK(hipMallocAsync(&part.p, (size_t)p.ntiles * (N + 2) * sizeof(double), s));
-        p.part = (double*)part.p;
-    }
-    RC_HIP_CHECK((hipError_t)rc_grad_launch(N, (void*)s, &p, mean));
-    return RC_OK;
-}
-
 int rc_mc_fidelity_grad_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
                                   const double* controllers_dev, const double* draws_dev, long long draws_ctrl_stride, long long C,
                                   long long K, double* fid_out_dev, double* grad_out_dev, double* mean_out_dev) {
     bool empty = false;
-    if (int rc = check_grad_args(N, in, out, controllers_dev, draws_dev, &draws_ctrl_stride, C, K, fid_out_dev, grad_out_dev,
-                                 mean_out_dev, &empty))
+    if (int rc = check_deriv_args("fidelity-gradient", kGradOuts, N, in, out, controllers_dev, draws_dev, &draws_ctrl_stride, 0.0,
+                                  nullptr, C, K, fid_out_dev || grad_out_dev || mean_out_dev, &empty))
         return rc;
     if (empty) return RC_OK;
     RC_HIP_CHECK(hipSetDevice(device));
@@ -1543,165 +1617,15 @@ int rc_mc_fidelity_grad_f64(int device, int N, int in, int out, const double* h0
                             const double* controllers, const double* draws, long long draws_ctrl_stride, long long C, long long K,
                             double* fid_out, double* grad_out, double* mean_out) {
     bool empty = false;
-    if (int rc = check_grad_args(N, in, out, controllers, draws, &draws_ctrl_stride, C, K, fid_out, grad_out, mean_out, &empty))
+    if (int rc = check_deriv_args("fidelity-gradient", kGradOuts, N, in, out, controllers, draws, &draws_ctrl_stride, 0.0, nullptr, C, K,
+                                  fid_out || grad_out || mean_out, &empty))
         return rc;
     if (empty) return RC_OK;
-    if (int rc = device_in_range(device)) return rc;
-    std::lock_guard<std::mutex> lk(g_ctx[device].mu);
-    DeviceCtx* ctx = nullptr;
-    if (int rc = get_ctx(device, &ctx)) return rc;
-    const size_t nb_ctrl = (size_t)C * (N + 1) * sizeof(double);
-    const size_t nb_draw = (draws_ctrl_stride == 0 ? (size_t)K * N * 3 : ((size_t)(C - 1) * draws_ctrl_stride + (size_t)K * N * 3)) *
-                           sizeof(double);
-    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_grad = nb_fid * (N + 1), nb_mean = (size_t)C * (N + 2) * sizeof(double);
-    const bool dc = is_device_ptr(controllers), dd = is_device_ptr(draws);
-    const bool hf = fid_out && !is_device_ptr(fid_out), hg = grad_out && !is_device_ptr(grad_out),
-               hm = mean_out && !is_device_ptr(mean_out);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t need = (dc ? 0 : up(nb_ctrl)) + (dd ? 0 : up(nb_draw)) + (hf ? up(nb_fid) : 0) + (hg ? up(nb_grad) : 0) +
-                        (hm ? up(nb_mean) : 0);
-    if (need) {
-        if (int rc = ensure_ws(ctx, need)) return rc;
-    }
-    char* w = (char*)ctx->ws;
-    const double* d_ctrl = controllers;
-    const double* d_draw = draws;
-    double *d_fid = fid_out, *d_grad = grad_out, *d_mean = mean_out;
-    if (!dc) {
-        RC_HIP_CHECK(hipMemcpyAsync(w, controllers, nb_ctrl, hipMemcpyHostToDevice, ctx->stream));
-        d_ctrl = (const double*)w;
-        w += up(nb_ctrl);
-    }
-    if (!dd) {
-        RC_HIP_CHECK(hipMemcpyAsync(w, draws, nb_draw, hipMemcpyHostToDevice, ctx->stream));
-        d_draw = (const double*)w;
-        w += up(nb_draw);
-    }
-    if (hf) { d_fid = (double*)w; w += up(nb_fid); }
-    if (hg) { d_grad = (double*)w; w += up(nb_grad); }
-    if (hm) { d_mean = (double*)w; w += up(nb_mean); }
-    if (int rc = enqueue_grad(ctx->stream, N, in, out, h0_diag, h0_offdiag, d_ctrl, d_draw, draws_ctrl_stride, C, K, d_fid, d_grad,
-                              d_mean))
-        return rc;
-    if (hf) RC_HIP_CHECK(hipMemcpyAsync(fid_out, d_fid, nb_fid, hipMemcpyDeviceToHost, ctx->stream));
-    if (hg) RC_HIP_CHECK(hipMemcpyAsync(grad_out, d_grad, nb_grad, hipMemcpyDeviceToHost, ctx->stream));
-    if (hm) RC_HIP_CHECK(hipMemcpyAsync(mean_out, d_mean, nb_mean, hipMemcpyDeviceToHost, ctx->stream));
-    RC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return RC_OK;
+    return blocking_deriv(enqueue_grad, N + 1, N + 2, device, N, in, out, h0_diag, h0_offdiag, controllers, draws, draws_ctrl_stride, C,
+                          K, fid_out, grad_out, mean_out);
 }
 
-long long rc_stats_grad_general_tiles(int device, int reset) {
-    if (hipSetDevice(device) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(RC_EHIP, "hipSetDevice failed");
-    }
-    unsigned long long v = 0;
-    void* addr = nullptr;
-    if (hipDeviceSynchronize() != hipSuccess || rc_grad_counter_addr(&addr) != hipSuccess || !addr ||
-        hipMemcpy(&v, addr, sizeof v, hipMemcpyDeviceToHost) != hipSuccess ||
-        (reset && hipMemset(addr, 0, sizeof v) != hipSuccess)) {
-        (void)hipGetLastError();
-        return fail(RC_EHIP, "reading the gradient kernel's tile counter failed");
-    }
-    return (long long)v;
-}
-
-// device pointers; the arguments have been checked
-static int enqueue_sens(hipStream_t s, int N, int in, int out, const double* h0_diag, const double* h0_offdiag, const double* ctrl,
-                        const double* draws, long long draw_cstride, long long C, long long K, double* fid, double* sens,
-                        double* mean) {
-    rckp::SensParams p{};
-    p.ctrl = ctrl;
-    p.draws = draws;
-    p.fid = fid;
-    p.sens = sens;
-    p.part = nullptr;
-    p.C = C;
-    p.K = K;
-    p.draw_cstride = draw_cstride;
-    p.tiles_per_ctrl = (K + 63) / 64;
-    p.ntiles = C * p.tiles_per_ctrl;
-    p.in = in;
-    p.out = out;
-    p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
-    for (int i = 0; i < RC_MAX_NSPIN; ++i) {
-        p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
-        p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
-    }
-    StreamFree part{nullptr, s};                     // per-tile sums of the row means: stream-ordered, released behind the second pass
-    if (mean) {
-        RC_HIP_CHECK(hipMallocAsync(&part.p, (size_t)p.ntiles * (3 * N + 2) * sizeof(double), s));
-        p.part = (double*)part.p;
-    }
-    RC_HIP_CHECK((hipError_t)rc_sens_launch(N, (void*)s, &p, mean));
-    return RC_OK;
-}
-
-int rc_mc_fidelity_sens_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
-                                  const double* controllers_dev, const double* draws_dev, long long draws_ctrl_stride, long long C,
-                                  long long K, double* fid_out_dev, double* sens_out_dev, double* mean_out_dev) {
-    bool empty = false;
-    if (int rc = check_grad_args(N, in, out, controllers_dev, draws_dev, &draws_ctrl_stride, C, K, fid_out_dev, sens_out_dev,
-                                 mean_out_dev, &empty, "noise-sensitivity", "sens_out"))
-        return rc;
-    if (empty) return RC_OK;
-    RC_HIP_CHECK(hipSetDevice(device));
-    return enqueue_sens((hipStream_t)stream, N, in, out, h0_diag, h0_offdiag, controllers_dev, draws_dev, draws_ctrl_stride, C, K,
-                        fid_out_dev, sens_out_dev, mean_out_dev);
-}
-
-int rc_mc_fidelity_sens_f64(int device, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
-                            const double* controllers, const double* draws, long long draws_ctrl_stride, long long C, long long K,
-                            double* fid_out, double* sens_out, double* mean_out) {
-    bool empty = false;
-    if (int rc = check_grad_args(N, in, out, controllers, draws, &draws_ctrl_stride, C, K, fid_out, sens_out, mean_out, &empty,
-                                 "noise-sensitivity", "sens_out"))
-        return rc;
-    if (empty) return RC_OK;
-    if (int rc = device_in_range(device)) return rc;
-    std::lock_guard<std::mutex> lk(g_ctx[device].mu);
-    DeviceCtx* ctx = nullptr;
-    if (int rc = get_ctx(device, &ctx)) return rc;
-    const size_t nb_ctrl = (size_t)C * (N + 1) * sizeof(double);
-    const size_t nb_draw = (draws_ctrl_stride == 0 ? (size_t)K * N * 3 : ((size_t)(C - 1) * draws_ctrl_stride + (size_t)K * N * 3)) *
-                           sizeof(double);
-    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_sens = nb_fid * 3 * N, nb_mean = (size_t)C * (3 * N + 2) * sizeof(double);
-    const bool dc = is_device_ptr(controllers), dd = is_device_ptr(draws);
-    const bool hf = fid_out && !is_device_ptr(fid_out), hs = sens_out && !is_device_ptr(sens_out),
-               hm = mean_out && !is_device_ptr(mean_out);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t need = (dc ? 0 : up(nb_ctrl)) + (dd ? 0 : up(nb_draw)) + (hf ? up(nb_fid) : 0) + (hs ? up(nb_sens) : 0) +
-                        (hm ? up(nb_mean) : 0);
-    if (need) {
-        if (int rc = ensure_ws(ctx, need)) return rc;
-    }
-    char* w = (char*)ctx->ws;
-    const double* d_ctrl = controllers;
-    const double* d_draw = draws;
-    double *d_fid = fid_out, *d_sens = sens_out, *d_mean = mean_out;
-    if (!dc) {
-        RC_HIP_CHECK(hipMemcpyAsync(w, controllers, nb_ctrl, hipMemcpyHostToDevice, ctx->stream));
-        d_ctrl = (const double*)w;
-        w += up(nb_ctrl);
-    }
-    if (!dd) {
-        RC_HIP_CHECK(hipMemcpyAsync(w, draws, nb_draw, hipMemcpyHostToDevice, ctx->stream));
-        d_draw = (const double*)w;
-        w += up(nb_draw);
-    }
-    if (hf) { d_fid = (double*)w; w += up(nb_fid); }
-    if (hs) { d_sens = (double*)w; w += up(nb_sens); }
-    if (hm) { d_mean = (double*)w; w += up(nb_mean); }
-    if (int rc = enqueue_sens(ctx->stream, N, in, out, h0_diag, h0_offdiag, d_ctrl, d_draw, draws_ctrl_stride, C, K, d_fid, d_sens,
-                              d_mean))
-        return rc;
-    if (hf) RC_HIP_CHECK(hipMemcpyAsync(fid_out, d_fid, nb_fid, hipMemcpyDeviceToHost, ctx->stream));
-    if (hs) RC_HIP_CHECK(hipMemcpyAsync(sens_out, d_sens, nb_sens, hipMemcpyDeviceToHost, ctx->stream));
-    if (hm) RC_HIP_CHECK(hipMemcpyAsync(mean_out, d_mean, nb_mean, hipMemcpyDeviceToHost, ctx->stream));
-    RC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return RC_OK;
-}
-
+// one unsigned 64-bit counter of the third unit, behind rc_grad_counter_addr / rc_sens_counter_addr (synchronises the device)
 static long long read_tile_counter(int device, int reset, int (*addr_of)(void**), const char* what) {
     if (hipSetDevice(device) != hipSuccess) {
         (void)hipGetLastError();
@@ -1718,6 +1642,35 @@ static long long read_tile_counter(int device, int reset, int (*addr_of)(void**)
     return (long long)v;
 }
 
+long long rc_stats_grad_general_tiles(int device, int reset) {
+    return read_tile_counter(device, reset, rc_grad_counter_addr, "reading the gradient kernel's tile counter failed");
+}
+
+int rc_mc_fidelity_sens_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
+                                  const double* controllers_dev, const double* draws_dev, long long draws_ctrl_stride, long long C,
+                                  long long K, double* fid_out_dev, double* sens_out_dev, double* mean_out_dev) {
+    bool empty = false;
+    if (int rc = check_deriv_args("noise-sensitivity", kSensOuts, N, in, out, controllers_dev, draws_dev, &draws_ctrl_stride, 0.0,
+                                  nullptr, C, K, fid_out_dev || sens_out_dev || mean_out_dev, &empty))
+        return rc;
+    if (empty) return RC_OK;
+    RC_HIP_CHECK(hipSetDevice(device));
+    return enqueue_sens((hipStream_t)stream, N, in, out, h0_diag, h0_offdiag, controllers_dev, draws_dev, draws_ctrl_stride, C, K,
+                        fid_out_dev, sens_out_dev, mean_out_dev);
+}
+
+int rc_mc_fidelity_sens_f64(int device, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
+                            const double* controllers, const double* draws, long long draws_ctrl_stride, long long C, long long K,
+                            double* fid_out, double* sens_out, double* mean_out) {
+    bool empty = false;
+    if (int rc = check_deriv_args("noise-sensitivity", kSensOuts, N, in, out, controllers, draws, &draws_ctrl_stride, 0.0, nullptr, C, K,
+                                  fid_out || sens_out || mean_out, &empty))
+        return rc;
+    if (empty) return RC_OK;
+    return blocking_deriv(enqueue_sens, 3 * N, 3 * N + 2, device, N, in, out, h0_diag, h0_offdiag, controllers, draws, draws_ctrl_stride,
+                          C, K, fid_out, sens_out, mean_out);
+}
+
 long long rc_stats_sens_general_tiles(int device, int reset) {
     return read_tile_counter(device, reset, rc_sens_counter_addr, "reading the sensitivity kernel's tile counter failed");
 }
@@ -1726,45 +1679,22 @@ int rc_mc_fidelity_sens_philox_f64_async(int device, void* stream, int N, int in
                                          const double* h0_offdiag, const double* controllers_dev, unsigned long long seed,
                                          unsigned long long offset, double sigma, const double* sigma_rows_dev, long long C,
                                          long long K, double* fid_out_dev, double* sens_out_dev, double* mean_out_dev) {
-    if (int rc = check_common(N, in, out, C, K)) return rc;
-    if (N > RC_MAX_NSPIN_GRAD)
-        return fail(RC_ENOSUP, "the noise-sensitivity kernel with draws generated inside it supports chains of N <= " +
-                                   std::to_string(RC_MAX_NSPIN_GRAD) + " spins");
-    if (!fid_out_dev && !sens_out_dev && !mean_out_dev)
-        return fail(RC_EINVAL, "no output requested (fid_out, sens_out and mean_out are all NULL)");
-    if (!sigma_rows_dev && !(sigma >= 0.0 && sigma < HUGE_VAL))
-        return fail(RC_EINVAL, "sigma must be finite and non-negative (or give sigma_rows)");
-    if (C == 0 || K == 0) return RC_OK;
-    if (!controllers_dev) return fail(RC_EINVAL, "NULL array pointer");
-    if ((C * ((K + 63) / 64)) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    bool empty = false;
+    if (int rc = check_deriv_args("noise-sensitivity", kSensOuts, N, in, out, controllers_dev, nullptr, nullptr, sigma, sigma_rows_dev, C,
+                                  K, fid_out_dev || sens_out_dev || mean_out_dev, &empty))
+        return rc;
+    if (empty) return RC_OK;
     RC_HIP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
     rckp::SensPhiloxParams p{};
-    p.ctrl = controllers_dev;
-    p.fid = fid_out_dev;
+    fill_deriv_params(p, N, in, out, h0_diag, h0_offdiag, controllers_dev, C, K, fid_out_dev);
     p.sens = sens_out_dev;
-    p.part = nullptr;
-    p.C = C;
-    p.K = K;
-    p.tiles_per_ctrl = (K + 63) / 64;
-    p.ntiles = C * p.tiles_per_ctrl;
-    p.in = in;
-    p.out = out;
     p.seed = seed;
     p.offset = offset;
     p.sigma_rows = sigma_rows_dev;
     p.sigma = sigma;
-    for (int i = 0; i < RC_MAX_NSPIN; ++i) {
-        p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
-        p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
-    }
-    StreamFree part{nullptr, s};                     // per-tile sums of the row means, as in enqueue_sens
-    if (mean_out_dev) {
-        RC_HIP_CHECK(hipMallocAsync(&part.p, (size_t)p.ntiles * (3 * N + 2) * sizeof(double), s));
-        p.part = (double*)part.p;
-    }
-    RC_HIP_CHECK((hipError_t)rc_sens_philox_launch(N, (void*)s, &p, mean_out_dev));
-    return RC_OK;
+    return launch_with_part(s, p, mean_out_dev != nullptr, 3 * N + 2, "rc_sens_philox_launch",
+                            [&] { return rc_sens_philox_launch(N, (void*)s, &p, mean_out_dev); });
 }
 
 int rc_mc_fidelity_grad_philox_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,
@@ -1772,47 +1702,25 @@ int rc_mc_fidelity_grad_philox_f64_async(int device, void* stream, int N, int in
                                          unsigned long long offset, double sigma, const double* sigma_rows_dev, int shared_draws,
                                          long long C, long long K, double* fid_out_dev, double* grad_out_dev, double* mean_out_dev,
                                          double* moment_out_dev) {
-    if (int rc = check_common(N, in, out, C, K)) return rc;
-    if (N > RC_MAX_NSPIN_GRAD)
-        return fail(RC_ENOSUP, "the fidelity-gradient kernel with draws generated inside it supports chains of N <= " +
-                                   std::to_string(RC_MAX_NSPIN_GRAD) + " spins");
-    if (!fid_out_dev && !grad_out_dev && !mean_out_dev && !moment_out_dev)
-        return fail(RC_EINVAL, "no output requested (fid_out, grad_out, mean_out and moment_out are all NULL)");
-    if (!sigma_rows_dev && !(sigma >= 0.0 && sigma < HUGE_VAL))
-        return fail(RC_EINVAL, "sigma must be finite and non-negative (or give sigma_rows)");
-    if (C == 0 || K == 0) return RC_OK;
-    if (!controllers_dev) return fail(RC_EINVAL, "NULL array pointer");
-    if ((C * ((K + 63) / 64)) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    bool empty = false;
+    if (int rc = check_deriv_args("fidelity-gradient", "fid_out, grad_out, mean_out and moment_out", N, in, out, controllers_dev, nullptr,
+                                  nullptr, sigma, sigma_rows_dev, C, K, fid_out_dev || grad_out_dev || mean_out_dev || moment_out_dev,
+                                  &empty))
+        return rc;
+    if (empty) return RC_OK;
     RC_HIP_CHECK(hipSetDevice(device));
     hipStream_t s = (hipStream_t)stream;
     rckp::GradPhiloxParams p{};
-    p.ctrl = controllers_dev;
-    p.fid = fid_out_dev;
+    fill_deriv_params(p, N, in, out, h0_diag, h0_offdiag, controllers_dev, C, K, fid_out_dev);
     p.grad = grad_out_dev;
-    p.part = nullptr;
-    p.C = C;
-    p.K = K;
-    p.tiles_per_ctrl = (K + 63) / 64;
-    p.ntiles = C * p.tiles_per_ctrl;
-    p.in = in;
-    p.out = out;
     p.shared = shared_draws ? 1 : 0;
     p.moments = moment_out_dev ? 1 : 0;
     p.seed = seed;
     p.offset = offset;
     p.sigma_rows = sigma_rows_dev;
     p.sigma = sigma;
-    for (int i = 0; i < RC_MAX_NSPIN; ++i) {
-        p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
-        p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
-    }
-    StreamFree part{nullptr, s};                     // per-tile sums of the row means (and moments), as in enqueue_grad
-    if (mean_out_dev || moment_out_dev) {
-        RC_HIP_CHECK(hipMallocAsync(&part.p, (size_t)p.ntiles * (N + 2) * (p.moments ? 2 : 1) * sizeof(double), s));
-        p.part = (double*)part.p;
-    }
-    RC_HIP_CHECK((hipError_t)rc_grad_philox_launch(N, (void*)s, &p, mean_out_dev, moment_out_dev));
-    return RC_OK;
+    return launch_with_part(s, p, mean_out_dev || moment_out_dev, (N + 2) * (p.moments ? 2 : 1), "rc_grad_philox_launch",
+                            [&] { return rc_grad_philox_launch(N, (void*)s, &p, mean_out_dev, moment_out_dev); });
 }
 
 int rc_mc_fidelity_philox_f64_async(int device, void* stream, int kernel, int N, int in, int out, const double* h0_diag,
@@ -1839,10 +1747,7 @@ int rc_mc_fidelity_philox_f64_async(int device, void* stream, int kernel, int N,
     p.in = in;
     p.out = out;
     p.align16 = 0;
-    for (int i = 0; i < RC_MAX_NSPIN; ++i) {
-        p.h0.diag[i] = (h0_diag && i < N) ? h0_diag[i] : 0.0;
-        p.h0.off[i] = (i < N - 1) ? (h0_offdiag ? h0_offdiag[i] : 1.0) : 0.0;
-    }
+    fill_h0(p.h0, N, h0_diag, h0_offdiag);
     PhiloxDraws q{seed, offset, sigma_rows_dev, sigma};
     hipStream_t s = (hipStream_t)stream;
     switch (N) {
