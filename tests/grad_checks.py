@@ -13,9 +13,11 @@ and for the mean over a row the same with the row's largest scale."""
 import numpy as np
 
 import chain_checks as cc
+from oracle import philox_host
 from oracle import robchar_oracle as orc
 
 TOL = cc.TOL
+EPS = 2.0 ** -52
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -116,6 +118,45 @@ def closed_form_grad(N, ctrl, inspin, outspin, lam=1.0):
 
 
 # ------------------------------------------------------------------------------------------------------------------------
+# static Hamiltonian terms shared by the tests of the kernels that generate their draws
+# ------------------------------------------------------------------------------------------------------------------------
+
+
+def static_cases(N):
+    """names of the static-term cases for an N-spin chain: "xxz" (h0_diag = the XXZ diagonal), "off" (non-unit h0_offdiag of
+    both signs), "both".  At N = 2 the XXZ diagonal is uniform - a global phase - so "xxz" alone changes nothing and is left out."""
+    return ("off", "both") if N == 2 else ("xxz", "off", "both")
+
+
+def static_terms(N, case):
+    """(h0_diag, h0_offdiag) of a case of `static_cases`; None = the default.  The couplings are U(0.6, 1.4) with the sign
+    flipped on every odd bond: negative static couplings are legal, and they are what tells re / r from |re| / r."""
+    off = np.random.default_rng(N).uniform(0.6, 1.4, N - 1)
+    off[1::2] *= -1.0
+    return (orc.xxz_delta(N) if case in ("xxz", "both") else None), (off if case in ("off", "both") else None)
+
+
+def static_hh(N, case="both"):
+    """the `HH` matrix of a noise model that carries the static terms of a case: chain hopping h0_offdiag, diagonal h0_diag"""
+    h0d, h0o = static_terms(N, case)
+    hop = np.arange(1, N)
+    HH = np.zeros((N, N), dtype=np.complex128)
+    HH[hop, hop - 1] = HH[hop - 1, hop] = np.ones(N - 1) if h0o is None else h0o
+    HH[np.arange(N), np.arange(N)] = 0.0 if h0d is None else h0d
+    return HH
+
+
+def assert_static_teeth(F_with, F_without, what=""):
+    """The static terms must matter: median |F(with the terms) - F(without)| >= 1e-2 over the non-NaN rows of the REFERENCE, or a
+    kernel that drops them would pass."""
+    F_with, F_without = np.asarray(F_with), np.asarray(F_without)
+    ok = ~np.isnan(F_with).any(axis=-1)
+    med = float(np.median(np.abs(F_with[ok] - F_without[ok])))
+    assert med >= 1e-2, ("the static terms do not change the reference fidelity enough to be missed", what, med)
+    return med
+
+
+# ------------------------------------------------------------------------------------------------------------------------
 # bounds
 # ------------------------------------------------------------------------------------------------------------------------
 
@@ -180,9 +221,47 @@ class Worst:
 # ------------------------------------------------------------------------------------------------------------------------
 
 
+PHILOX_OUTPUTS = ("fid", "grad", "mean", "moment")
+WRAP = 2 ** 33                       # the stream element at which the low word of the Box-Muller pair counter (element >> 1) wraps
+
+
+def host_draws(seed, offset, shape, scale, lost_carry=False):
+    """oracle/philox_host.py draws in the layout of `backend.philox_normal`; `scale` a float or one value per leading row.
+    `lost_carry` is a deliberately WRONG variant for the checks' own tests: the pair counter's high word stays that of the first
+    element, so elements behind a multiple of 2^33 repeat the stream 2^33 elements earlier."""
+    n = int(np.prod(shape))
+    cut = (offset // WRAP + 1) * WRAP
+    if lost_carry and offset < cut < offset + n:
+        flat = np.concatenate([philox_host.philox_normal(seed, offset, cut - offset),
+                               philox_host.philox_normal(seed, cut - WRAP, offset + n - cut)])
+    else:
+        flat = philox_host.philox_normal(seed, offset, n)
+    z = flat.reshape(shape)
+    scale = np.asarray(scale, dtype=np.float64)
+    return z * (scale.reshape((-1,) + (1,) * (z.ndim - 1)) if scale.ndim else float(scale))
+
+
+def _dropped(broken, h0_diag, h0_offdiag, fused=False):
+    """the static terms as a broken stand-in sees them"""
+    if broken == "no_h0_diag":
+        h0_diag = None
+    if broken == "no_h0_offdiag" or (fused and broken == "philox_no_h0_offdiag"):
+        h0_offdiag = None
+    return h0_diag, h0_offdiag
+
+
+def _row_mean(x, K, broken):
+    """the mean over axis 1; broken "mean_64_tiles": only the first 64 tiles of 64 samples are added"""
+    if x.shape[1] == 0:
+        return np.zeros(x.shape[:1] + x.shape[2:])
+    return x[:, :4096].sum(axis=1) / K if broken == "mean_64_tiles" else x.mean(axis=1)
+
+
 class StandIn:
-    """`mc_fidelity_grad` / `mc_fidelity` of the backend on the CPU.  broken: None, "zeros", "time_sign" (sign of the time
-    entry dropped for negative x_N), "reversed" (bias entries in reversed order), "gamma_diag" (Gam_jk = Gam_kk)."""
+    """`mc_fidelity_grad` / `mc_fidelity` / `philox_normal` / `mc_fidelity_grad_philox` of the backend on the CPU.  broken: None,
+    "zeros", "time_sign" (sign of the time entry dropped for negative x_N), "reversed" (bias entries in reversed order),
+    "gamma_diag" (Gam_jk = Gam_kk), "no_h0_diag" / "no_h0_offdiag" (the static term ignored), and in the entry that generates
+    its draws only: "philox_no_h0_offdiag", "lost_carry" (`host_draws`), "mean_64_tiles" (row sums stop after 64 tiles)."""
 
     def __init__(self, broken=None):
         self.broken = broken
@@ -190,8 +269,13 @@ class StandIn:
     def mc_fidelity(self, ctrl, draws, N, a, b, h0_diag=None, h0_offdiag=None, kernel="auto"):
         return grad_eigh(ctrl, draws, N, a, b, h0_diag, h0_offdiag)[0]
 
-    def mc_fidelity_grad(self, ctrl, draws, N, a, b, h0_diag=None, h0_offdiag=None, device=None, want=("fid", "grad", "mean")):
+    def philox_normal(self, shape, seed, scale=1.0, offset=0):
+        return host_draws(seed, offset, shape, scale)
+
+    def mc_fidelity_grad(self, ctrl, draws, N, a, b, h0_diag=None, h0_offdiag=None, device=None, want=("fid", "grad", "mean"),
+                         _fused=False):
         ctrl = np.asarray(ctrl, dtype=np.float64)
+        h0_diag, h0_offdiag = _dropped(self.broken, h0_diag, h0_offdiag, _fused)
         F, G = grad_eigh(ctrl, draws, N, a, b, h0_diag, h0_offdiag, gamma_diag_only=self.broken == "gamma_diag")
         if self.broken == "zeros":
             G = np.where(np.isnan(G), G, 0.0)
@@ -199,14 +283,28 @@ class StandIn:
             G[..., N] = np.sign(ctrl[:, N])[:, None] * G[..., N]          # = 2 Re(conj(phi) dphi/dT) without the sign
         elif self.broken == "reversed":
             G[..., :N] = G[..., :N][..., ::-1]
+        K, bm = F.shape[1], self.broken if _fused else None
         res = {}
         if "fid" in want:
             res["fid"] = F
         if "grad" in want:
             res["grad"] = G
         if "mean" in want:
-            res["mean"] = np.concatenate([F.mean(axis=1)[:, None], G.mean(axis=1)], axis=1) if F.shape[1] else np.zeros((F.shape[0], N + 2))
+            res["mean"] = np.concatenate([_row_mean(F, K, bm)[:, None], _row_mean(G, K, bm)], axis=1)
+        if "moment" in want:
+            res["moment"] = np.concatenate([_row_mean(F * F, K, bm)[:, None], _row_mean(F[..., None] * G, K, bm)], axis=1)
         return res
+
+    def mc_fidelity_grad_philox(self, ctrl, K, N, a, b, seed, offset=0, sigma=0.05, shared=False, h0_diag=None, h0_offdiag=None,
+                                want=PHILOX_OUTPUTS):
+        ctrl = np.asarray(ctrl, dtype=np.float64)
+        C = ctrl.shape[0]
+        if shared:
+            draws = host_draws(seed, offset, (1, K, N, 3), 1.0, self.broken == "lost_carry")
+            draws = draws * np.broadcast_to(sigma, (C,))[:, None, None, None]
+        else:
+            draws = host_draws(seed, offset, (C, K, N, 3), sigma, self.broken == "lost_carry")
+        return self.mc_fidelity_grad(ctrl, draws, N, a, b, h0_diag, h0_offdiag, want=want, _fused=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -237,7 +335,8 @@ def _check_one(be, ctrl, draws, N, a, b, what, worst, key, h0_diag=None, h0_offd
 
 def check_deloc_grad(be, N, worst=None):
     """Delocalised rows (chain_checks.deloc_ctrl), K = 192 (three tiles), sigma = 0.05, one NaN row, one row with a negative
-    time entry; pairs end to end both ways, interior, in == out; a ragged K = 100 case; XXZ offsets."""
+    time entry; pairs end to end both ways, interior, in == out; a ragged K = 100 case; XXZ offsets; non-unit static couplings
+    of both signs (`static_terms`) under random draws, with the guard that they matter."""
     rng = np.random.default_rng(5200 + N)
     C, K = 5, 192
     ctrl = cc.deloc_ctrl(rng, C, N, 0.5)
@@ -250,6 +349,9 @@ def check_deloc_grad(be, N, worst=None):
     d2 = 0.05 * rng.standard_normal((2, 100, N, 3))
     _check_one(be, c2, d2, N, 0, N - 1, ("deloc ragged", N), worst, ("deloc", N))
     _check_one(be, c2, d2, N, N - 1, 0, ("deloc xxz", N), worst, ("deloc", N), h0_diag=orc.xxz_delta(N))
+    off = static_terms(N, "off")[1]
+    assert_static_teeth(grad_eigh(c2, d2, N, 0, N - 1, None, off)[0], grad_eigh(c2, d2, N, 0, N - 1)[0], ("deloc offdiag", N))
+    _check_one(be, c2, d2, N, 0, N - 1, ("deloc offdiag", N), worst, ("deloc", N), h0_offdiag=off)
 
 
 def check_closed_form_grad(be, N, worst=None):
@@ -341,3 +443,150 @@ def check_mean_and_shared(be, N=7):
     assert set(only) == {"mean"} and np.array_equal(only["mean"], r1["mean"])
     only = be.mc_fidelity_grad(ctrl, shared, N, 0, N - 1, want=("grad",))
     assert set(only) == {"grad"} and np.array_equal(only["grad"], r1["grad"])
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# checks of the entry that generates its draws (`mc_fidelity_grad_philox`): static terms, long rows, far stream offsets
+# ------------------------------------------------------------------------------------------------------------------------
+
+PHILOX_SEED = 0x5EED000A
+PHILOX_SIGMA = 0.05
+FAR_OFFSET = 123456789012345
+
+
+def wrap_offset(N):
+    """odd, and the pair counter's low word wraps to 0 inside lane 32's sample of the first tile (3 N elements per sample)"""
+    return WRAP - 32 * 3 * N - 1
+
+
+# controller seeds of the static-term cases where 9300 + N falls under a guard: at N = 3 the "off" case, 0 -> 2, has a median
+# |dF/dx_l| of 0.0084 on the rows of seed 9303, under the 1e-2 of assert_grad_teeth; on those of seed 9503 it is 0.055
+STATIC_CTRL_SEED = {3: 9503}
+
+
+def philox_ctrl(N, C=3, nan_row=1, neg_row=2, seed=None):
+    """delocalised rows (the gradients have teeth there), one of them NaN, one with a negative time entry"""
+    ctrl = cc.deloc_ctrl(np.random.default_rng(9300 + N if seed is None else seed), C, N, 0.5)
+    if neg_row is not None:
+        ctrl[neg_row, N] = -ctrl[neg_row, N]
+    if nan_row is not None:
+        ctrl[nan_row, N // 2] = np.nan
+    return ctrl
+
+
+def to_host(res):
+    """a dict of NumPy arrays from a dict of NumPy arrays or torch tensors"""
+    return {k: (v.cpu().numpy() if hasattr(v, "cpu") else np.asarray(v)) for k, v in res.items()}
+
+
+def assert_same_bits(got, want, what, keys):
+    for k in keys:
+        assert got[k].shape == want[k].shape, (what, k)
+        assert np.array_equal(got[k], want[k], equal_nan=True), (
+            what, k, "differs in", int((~((got[k] == want[k]) | (np.isnan(got[k]) & np.isnan(want[k])))).sum()), "entries, max |diff|",
+            float(np.nanmax(np.abs(got[k] - want[k]))))
+
+
+def _fused(be, ctrl, K, N, a, b, offset, shared, h0d=None, h0o=None, sigma=PHILOX_SIGMA, want=PHILOX_OUTPUTS):
+    return to_host(be.mc_fidelity_grad_philox(ctrl, K, N, a, b, PHILOX_SEED, offset=offset, sigma=sigma, shared=shared, h0_diag=h0d,
+                                              h0_offdiag=h0o, want=want))
+
+
+def _two_kernels(be, ctrl, K, N, a, b, offset, shared, h0d=None, h0o=None, sigma=PHILOX_SIGMA):
+    draws = be.philox_normal((1 if shared else ctrl.shape[0], K, N, 3), PHILOX_SEED, scale=sigma, offset=offset)
+    return be.mc_fidelity_grad(ctrl, draws, N, a, b, h0_diag=h0d, h0_offdiag=h0o)
+
+
+def reference_on_host_draws(ctrl, K, N, a, b, offset, shared, h0d=None, h0o=None, sigma=PHILOX_SIGMA):
+    """(draws regenerated on the host, F, G of grad_eigh on them)"""
+    draws = host_draws(PHILOX_SEED, offset, (1 if shared else ctrl.shape[0], K, N, 3), sigma)
+    return (draws,) + grad_eigh(ctrl, draws, N, a, b, h0d, h0o)
+
+
+def _compare_with_reference(got, ctrl, draws, Fw, Gw, N, h0d, h0o, what):
+    bars = grad_bars(ctrl, draws, N, h0d, h0o)
+    cc.compare(got["fid"], Fw, (what, "fid"))
+    out = compare_grad(got["grad"], Gw, bars, (what, "grad"))
+    mw = np.concatenate([Fw.mean(axis=1)[:, None], Gw.mean(axis=1)], axis=1)
+    mb = np.concatenate([np.full((bars.shape[0], 1), TOL), bars.max(axis=1)], axis=1)
+    compare_grad(got["mean"], mw, mb, (what, "mean"))
+    return out
+
+
+def check_static_grad_philox(be, N, identity=True, reference=True, K=130, offsets=(0, 7), worst=None):
+    """Every case of `static_cases`, every pair of `grad_pairs`, both draw modes.  On the reference alone first: the static terms
+    change F (`assert_static_teeth`) and the gradient has teeth.  `identity`: fid, grad, mean carry the bits of `philox_normal` +
+    `mc_fidelity_grad` with the same terms.  `reference`: inside the bars of grad_eigh on host-regenerated draws."""
+    ctrl = philox_ctrl(N, seed=STATIC_CTRL_SEED.get(N))
+    for case in static_cases(N):
+        h0d, h0o = static_terms(N, case)
+        for (a, b) in grad_pairs(N):
+            for offset in offsets:
+                for shared in (False, True):
+                    what = ("static", case, N, a, b, offset, "shared" if shared else "per row")
+                    draws, Fw, Gw = reference_on_host_draws(ctrl, K, N, a, b, offset, shared, h0d, h0o)
+                    assert_static_teeth(Fw, grad_eigh(ctrl, draws, N, a, b)[0], what)
+                    assert_grad_teeth(Gw, what)
+                    got = _fused(be, ctrl, K, N, a, b, offset, shared, h0d, h0o)
+                    assert all(np.isnan(got[k][1]).all() for k in PHILOX_OUTPUTS) and np.isfinite(got["moment"][[0, 2]]).all(), what
+                    if identity:
+                        assert_same_bits(got, _two_kernels(be, ctrl, K, N, a, b, offset, shared, h0d, h0o), what, ("fid", "grad", "mean"))
+                    if reference:
+                        out = _compare_with_reference(got, ctrl, draws, Fw, Gw, N, h0d, h0o, what)
+                        if worst is not None:
+                            worst.add(("static", case, N), out)
+
+
+def host_moments(res):
+    return np.concatenate([(res["fid"] ** 2).mean(axis=1)[:, None], (res["fid"][..., None] * res["grad"]).mean(axis=1)], axis=1)
+
+
+def host_means(res):
+    return np.concatenate([res["fid"].mean(axis=1)[:, None], res["grad"].mean(axis=1)], axis=1)
+
+
+def check_long_rows_grad_philox(be, N, K, report=None):
+    """Rows of more than 64 tiles in the row-mean kernel (K = 4096: one tile per lane; 4097, 8193: a second and third step of the
+    strided loop), C = 3 with a NaN row, both draw modes, all four outputs: fid, grad, mean = the bits of the two-kernel route;
+    mean and moment within K 2^-52 max(1, max |entry|) of host sums of the same launch's per-sample outputs; the same bits on a
+    second run and from the launches that write row sums only."""
+    ctrl = philox_ctrl(N)
+    a, b, offset, ok = 0, N - 1, 7, [0, 2]
+    for shared in (False, True):
+        what = ("long rows", N, K, "shared" if shared else "per row")
+        full = _fused(be, ctrl, K, N, a, b, offset, shared)
+        assert_grad_teeth(full["grad"], what)
+        assert all(np.isnan(full[k][1]).all() for k in PHILOX_OUTPUTS), what
+        assert_same_bits(full, _two_kernels(be, ctrl, K, N, a, b, offset, shared), what, ("fid", "grad", "mean"))
+        bound = K * EPS * max(1.0, float(np.abs(full["grad"][ok]).max()))
+        e_mean = float(np.abs(full["mean"][ok] - host_means(full)[ok]).max())
+        e_mom = float(np.abs(full["moment"][ok] - host_moments(full)[ok]).max())
+        if report is not None:
+            report(f"long rows, N = {N}, K = {K}, shared = {shared}: |mean - host| = {e_mean:.2e} ({e_mean / bound:.2e} of the bound), "
+                   f"|moment - host| = {e_mom:.2e} ({e_mom / bound:.2e})")
+        assert e_mean <= bound, (what, "mean against host sums", e_mean, bound)
+        assert e_mom <= bound, (what, "moment against host sums", e_mom, bound)
+        assert np.abs(host_moments(full)[ok, 1:]).max() > 1e-3 and host_moments(full)[ok, 0].min() > 1e-3, what
+        assert_same_bits(_fused(be, ctrl, K, N, a, b, offset, shared), full, (what, "second run"), PHILOX_OUTPUTS)
+        for sub in (("moment",), ("mean", "moment")):
+            only = _fused(be, ctrl, K, N, a, b, offset, shared, want=sub)
+            assert set(only) == set(sub), (what, sub)
+            assert_same_bits(only, full, (what, sub), sub)
+
+
+def check_far_offsets_grad_philox(be, N, K=130, worst=None):
+    """Stream offsets whose pair counter has a non-zero high word (`FAR_OFFSET`) or carries into it inside the first tile
+    (`wrap_offset`), both draw modes: the bits of the two-kernel route and inside the bars of grad_eigh on host-regenerated
+    draws at the same offsets."""
+    ctrl = philox_ctrl(N)
+    for offset in (wrap_offset(N), FAR_OFFSET):
+        for (a, b) in grad_pairs(N)[:2]:
+            for shared in (False, True):
+                what = ("far offset", N, a, b, offset, "shared" if shared else "per row")
+                draws, Fw, Gw = reference_on_host_draws(ctrl, K, N, a, b, offset, shared)
+                assert_grad_teeth(Gw, what)
+                got = _fused(be, ctrl, K, N, a, b, offset, shared)
+                assert_same_bits(got, _two_kernels(be, ctrl, K, N, a, b, offset, shared), what, ("fid", "grad", "mean"))
+                out = _compare_with_reference(got, ctrl, draws, Fw, Gw, N, None, None, what)
+                if worst is not None:
+                    worst.add(("far offset", N), out)

@@ -176,40 +176,65 @@ def compare_sens(got, want, bars, what):
 # a NumPy stand-in backend and broken variants of it, for the checks' own CPU tests
 # ------------------------------------------------------------------------------------------------------------------------
 
-BROKEN = ("zeros", "no_phase", "swapped", "shifted", "diag_once", "rho_no_g0", "mean_by_tiles")
+BROKEN = ("zeros", "no_phase", "swapped", "shifted", "diag_once", "rho_no_g0", "mean_by_tiles", "no_h0_diag", "no_h0_offdiag", "re_g1")
+PHILOX_BROKEN = ("philox_no_h0_offdiag", "lost_carry", "mean_64_tiles")      # wrong in the entry that generates its draws only
+PHILOX_OUTPUTS = ("fid", "sens", "mean")
 
 
 class StandIn(gc.StandIn):
-    """`mc_fidelity_sens` (+ `mc_fidelity`, `mc_fidelity_grad` of grad_checks.StandIn) on the CPU.  broken: None or one of
-    BROKEN - "zeros"; "no_phase" (dF/dr in the g1 entry without re/r); "swapped" (g1 <-> g2); "shifted" (bond i stored at site
-    i - 1); "diag_once" (B_kk counted once); "rho_no_g0" (rho without the site part); "mean_by_tiles" (mean divided by the
-    number of tiles)."""
+    """`mc_fidelity_sens`, `mc_fidelity_sens_philox` (+ `mc_fidelity`, `mc_fidelity_grad`, `philox_normal` of grad_checks.StandIn)
+    on the CPU.  broken: None or one of BROKEN - "zeros"; "no_phase" (dF/dr in the g1 entry without re/r); "swapped" (g1 <-> g2);
+    "shifted" (bond i stored at site i - 1); "diag_once" (B_kk counted once); "rho_no_g0" (rho without the site part);
+    "mean_by_tiles" (mean divided by the number of tiles); "no_h0_diag" / "no_h0_offdiag" (the static term ignored); "re_g1"
+    (h0_offdiag in the matrix, but the chain rule from (r, theta) to (g1, g2) taken at re = g1) - or one of PHILOX_BROKEN, as in
+    grad_checks.StandIn."""
 
     def __init__(self, broken=None):
         super().__init__(None)
         self.sbroken = broken
 
-    def mc_fidelity_sens(self, ctrl, draws, N, a, b, h0_diag=None, h0_offdiag=None, device=None, want=("fid", "sens", "mean")):
+    def mc_fidelity_sens(self, ctrl, draws, N, a, b, h0_diag=None, h0_offdiag=None, device=None, want=("fid", "sens", "mean"),
+                         _fused=False):
         ctrl, draws = gc._bcast(ctrl, draws)
+        h0_diag, h0_offdiag = gc._dropped(self.sbroken, h0_diag, h0_offdiag, _fused)
         F, S = sens_eigh(ctrl, draws, N, a, b, h0_diag, h0_offdiag, diag_once=self.sbroken == "diag_once")
+        h0o = np.ones(N - 1) if h0_offdiag is None else np.asarray(h0_offdiag, dtype=np.float64)
+        re, im = h0o + draws[:, :, 1:, 1], draws[:, :, 1:, 2]
+        cut = (re == 0.0) & (im == 0.0) & ~np.isnan(S[:, :, 1:, 1])
+        # The contract, put in BY HAND (and `+ 0.0` on rho below, which turns a -0.0 into +0.0): both parts of an exactly cut bond
+        # are 0.0.  The sound stand-in passing check_cut_bond_sens_philox therefore shows only that the check can be met - it is no
+        # reference for the zero; the check's teeth are the broken variants "re_g1", "no_h0_offdiag" and "no_phase".
+        S[:, :, 1:, 1:][cut] = 0.0
         if self.sbroken == "zeros":
             S = np.where(np.isnan(S), S, 0.0)
         elif self.sbroken == "no_phase":
-            h0o = np.ones(N - 1) if h0_offdiag is None else np.asarray(h0_offdiag, dtype=np.float64)
-            re, im = h0o + draws[:, :, 1:, 1], draws[:, :, 1:, 2]
-            S[:, :, 1:, 1] = (re * S[:, :, 1:, 1] + im * S[:, :, 1:, 2]) / np.hypot(re, im)
+            with np.errstate(invalid="ignore"):
+                S[:, :, 1:, 1] = (re * S[:, :, 1:, 1] + im * S[:, :, 1:, 2]) / np.hypot(re, im)
+        elif self.sbroken == "re_g1":
+            # dF/dr = (re S1 + im S2) / r, dF/dtheta = re S2 - im S1; back to (g1, g2) with re' = g1 in place of h0 + g1
+            with np.errstate(invalid="ignore", divide="ignore"):
+                dr, dth = (re * S[:, :, 1:, 1] + im * S[:, :, 1:, 2]) / np.hypot(re, im), re * S[:, :, 1:, 2] - im * S[:, :, 1:, 1]
+                r1, r2 = draws[:, :, 1:, 1], np.hypot(draws[:, :, 1:, 1], im)
+                S[:, :, 1:, 1] = dr * r1 / r2 - dth * im / r2 ** 2
+                S[:, :, 1:, 2] = dr * im / r2 + dth * r1 / r2 ** 2
         elif self.sbroken == "swapped":
             S = S[..., [0, 2, 1]]
         elif self.sbroken == "shifted":
             S[:, :, :-1, 1:] = S[:, :, 1:, 1:].copy()
             S[:, :, -1, 1:] = 0.0
-        K = F.shape[1]
-        rho = radial(draws, S) if self.sbroken != "rho_no_g0" else (draws[..., 1:] * S[..., 1:]).sum(axis=(-1, -2))
-        M = np.concatenate([F.mean(axis=1)[:, None], rho.mean(axis=1)[:, None], S.mean(axis=1).reshape(F.shape[0], -1)], axis=1)
+        K, bm = F.shape[1], self.sbroken if _fused else None
+        rho = (radial(draws, S) if self.sbroken != "rho_no_g0" else (draws[..., 1:] * S[..., 1:]).sum(axis=(-1, -2))) + 0.0
+        M = np.concatenate([gc._row_mean(F, K, bm)[:, None], gc._row_mean(rho, K, bm)[:, None],
+                            gc._row_mean(S, K, bm).reshape(F.shape[0], -1)], axis=1)
         if self.sbroken == "mean_by_tiles":
             M = M * K / ((K + 63) // 64)
         res = {"fid": F, "sens": S, "mean": M}
         return {k: v for k, v in res.items() if k in want}
+
+    def mc_fidelity_sens_philox(self, ctrl, K, N, a, b, seed, offset=0, sigma=0.05, h0_diag=None, h0_offdiag=None, want=PHILOX_OUTPUTS):
+        ctrl = np.asarray(ctrl, dtype=np.float64)
+        draws = gc.host_draws(seed, offset, (ctrl.shape[0], K, N, 3), sigma, self.sbroken == "lost_carry")
+        return self.mc_fidelity_sens(ctrl, draws, N, a, b, h0_diag, h0_offdiag, want=want, _fused=True)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
@@ -341,3 +366,161 @@ def check_consistency(be, N):
     d = np.abs(r1["mean"] - rows)
     assert d.max() <= K * EPS * scale, ("mean against the row means", float(d.max()))
     return float(d.max())
+
+
+# ------------------------------------------------------------------------------------------------------------------------
+# checks of the entry that generates its draws (`mc_fidelity_sens_philox`): static terms, cut bond, long rows, far offsets
+# ------------------------------------------------------------------------------------------------------------------------
+
+PHILOX_SEED = 0x5EED0009
+PHILOX_SIGMA = 0.05
+
+
+def philox_ctrl(N, C=3, nan_row=1, seed=None):
+    """delocalised rows (the sensitivities have teeth there), one of them NaN"""
+    ctrl = cc.deloc_ctrl(np.random.default_rng(9100 + N if seed is None else seed), C, N, 0.5)
+    if nan_row is not None:
+        ctrl[nan_row, N // 2] = np.nan
+    return ctrl
+
+
+def _fused(be, ctrl, K, N, a, b, offset, h0d=None, h0o=None, sigma=PHILOX_SIGMA, want=PHILOX_OUTPUTS):
+    return gc.to_host(be.mc_fidelity_sens_philox(ctrl, K, N, a, b, PHILOX_SEED, offset=offset, sigma=sigma, h0_diag=h0d, h0_offdiag=h0o,
+                                                 want=want))
+
+
+def _two_kernels(be, ctrl, K, N, a, b, offset, h0d=None, h0o=None, sigma=PHILOX_SIGMA):
+    draws = be.philox_normal((ctrl.shape[0], K, N, 3), PHILOX_SEED, scale=sigma, offset=offset)
+    return be.mc_fidelity_sens(ctrl, draws, N, a, b, h0_diag=h0d, h0_offdiag=h0o)
+
+
+def reference_on_host_draws(ctrl, K, N, a, b, offset, h0d=None, h0o=None, sigma=PHILOX_SIGMA):
+    """(draws regenerated on the host, F, S of sens_eigh on them)"""
+    draws = gc.host_draws(PHILOX_SEED, offset, (ctrl.shape[0], K, N, 3), sigma)
+    return (draws,) + sens_eigh(ctrl, draws, N, a, b, h0d, h0o)
+
+
+def _compare_with_reference(got, ctrl, draws, Fw, Sw, N, what):
+    bars, rbars = sens_bars(ctrl, draws, N)
+    cc.compare(got["fid"], Fw, (what, "fid"))
+    out = compare_sens(got["sens"], Sw, bars, (what, "sens"))
+    compare_sens(got["mean"], mean_of(Fw, draws, Sw), mean_bars(bars, rbars), (what, "mean"))
+    return out
+
+
+def check_static_sens_philox(be, N, identity=True, reference=True, K=130, offsets=(0, 7), worst=None):
+    """grad_checks.check_static_grad_philox for the sensitivity entry: every case of grad_checks.static_cases and every pair of
+    grad_pairs; the guards on the reference alone, then the bits of the two-kernel route (`identity`) and the bars of sens_eigh on
+    host-regenerated draws (`reference`)."""
+    ctrl = philox_ctrl(N)
+    for case in gc.static_cases(N):
+        h0d, h0o = gc.static_terms(N, case)
+        for (a, b) in gc.grad_pairs(N):
+            for offset in offsets:
+                what = ("static", case, N, a, b, offset)
+                draws, Fw, Sw = reference_on_host_draws(ctrl, K, N, a, b, offset, h0d, h0o)
+                gc.assert_static_teeth(Fw, sens_eigh(ctrl, draws, N, a, b)[0], what)
+                assert_sens_teeth(Sw, what)
+                got = _fused(be, ctrl, K, N, a, b, offset, h0d, h0o)
+                assert all(np.isnan(got[k][1]).all() for k in PHILOX_OUTPUTS), what
+                if identity:
+                    gc.assert_same_bits(got, _two_kernels(be, ctrl, K, N, a, b, offset, h0d, h0o), what, PHILOX_OUTPUTS)
+                if reference:
+                    out = _compare_with_reference(got, ctrl, draws, Fw, Sw, N, what)
+                    if worst is not None:
+                        worst.add(("static", case, N), out)
+
+
+
+def cut_pairs(N):
+    """(in, out) pairs on one side of the bond between the sites m - 1 and m, m = max(1, N // 2) - F is not trivially 0 - and not
+    on a side of one site, where F = 1 whatever the controller"""
+    m = max(1, N // 2)
+    pairs = [(m, N - 1), (N - 1, N - 1)] + ([(0, m - 1)] if m >= 2 else [])
+    return m, tuple(dict.fromkeys(pairs))
+
+
+def check_cut_bond_sens_philox(be, N, K=130, worst=None):
+    """h0_offdiag[m - 1] = 0, sigma_rows = (0, 0.05).  The sigma = 0 row has r = 0 on that bond in every sample: everything finite,
+    both coupling derivatives of the bond exactly 0.0, the mean rho exactly +0.0.  The sigma = 0.05 row: inside the bars of
+    sens_eigh.  Both rows: the bits of the two-kernel route, row by row at the row's own offset."""
+    m, pairs = cut_pairs(N)
+    h0o = np.ones(N - 1)
+    h0o[m - 1] = 0.0
+    rows = np.array([0.0, PHILOX_SIGMA])
+    ctrl = philox_ctrl(N, C=2, nan_row=None)
+    ctrl[:, N] *= (N - m) / N                      # the time an excitation needs to cross the longer piece, not the whole chain
+    for (a, b) in pairs:
+        side = slice(m, N) if a >= m else slice(0, m)
+        for offset in (0, 7):
+            what = ("cut bond", N, a, b, offset)
+            draws, Fw, Sw = reference_on_host_draws(ctrl, K, N, a, b, offset, None, h0o, sigma=rows)
+            m0 = float(np.median(np.abs(Sw[:, :, side, 0])))
+            assert np.median(Fw) >= 1e-2 and m0 >= 1e-2, ("the cut-chain reference cannot tell a wrong kernel from a right one", what,
+                                                         float(np.median(Fw)), m0)
+            got = _fused(be, ctrl, K, N, a, b, offset, None, h0o, sigma=rows)
+            assert all(np.isfinite(got[k][0]).all() for k in PHILOX_OUTPUTS), (what, "sigma = 0 row not finite")
+            assert (got["sens"][0, :, m, 1:] == 0.0).all(), (what, "coupling derivatives of the cut bond", got["sens"][0, 0, m, 1:])
+            assert (got["mean"][0, 2:].reshape(N, 3)[m, 1:] == 0.0).all(), (what, "mean coupling derivatives of the cut bond")
+            rho0 = got["mean"][0, 1]
+            assert rho0 == 0.0 and not np.signbit(rho0), (what, "mean rho of the sigma = 0 row", rho0)
+            assert (got["sens"][0] == got["sens"][0, :1]).all() and (got["fid"][0] == got["fid"][0, 0]).all(), what
+            for c, sigma in enumerate(rows):
+                want = _two_kernels(be, ctrl[c:c + 1], K, N, a, b, offset + c * K * N * 3, None, h0o, sigma=float(sigma))
+                gc.assert_same_bits({k: got[k][c:c + 1] for k in PHILOX_OUTPUTS}, want, (what, "row", c), PHILOX_OUTPUTS)
+            out = _compare_with_reference(got, ctrl, draws, Fw, Sw, N, what)
+            if worst is not None:
+                worst.add(("cut bond", N), out)
+
+
+def _assert_mean_of_same_launch(res, draws, K, what, report=None):
+    ok = ~np.isnan(res["fid"]).any(axis=1)
+    rows = mean_of(res["fid"][ok], draws[ok], res["sens"][ok])
+    bound = K * EPS * max(1.0, float(np.abs(res["sens"][ok]).max()))
+    err = float(np.abs(res["mean"][ok] - rows).max())
+    if report is not None:
+        report(f"{what}: |mean - host row means| = {err:.2e} ({err / bound:.2e} of the bound)")
+    assert err <= bound, (what, "mean against the row means of the same launch", err, bound)
+
+
+def check_long_rows_sens_philox(be, N, K, report=None):
+    """Rows of more than 64 tiles in the row-mean kernel (3 N + 2 entries per part row), C = 3 with a NaN row, draws generated in
+    the kernel: mean bit-identical between the two routes and within K 2^-52 max(1, max |entry|) of the host row means of the
+    same launch's fid, rho and sens."""
+    ctrl = philox_ctrl(N)
+    a, b, offset = 0, N - 1, 7
+    what = ("long rows", N, K)
+    full = _fused(be, ctrl, K, N, a, b, offset)
+    assert_sens_teeth(full["sens"], what)
+    assert all(np.isnan(full[k][1]).all() for k in PHILOX_OUTPUTS), what
+    gc.assert_same_bits(full, _two_kernels(be, ctrl, K, N, a, b, offset), what, PHILOX_OUTPUTS)
+    draws = gc.host_draws(PHILOX_SEED, offset, (ctrl.shape[0], K, N, 3), PHILOX_SIGMA)
+    _assert_mean_of_same_launch(full, draws, K, f"long rows, generated draws, N = {N}, K = {K}", report)
+    only = _fused(be, ctrl, K, N, a, b, offset, want=("mean",))
+    gc.assert_same_bits(only, full, (what, "mean alone"), ("mean",))
+
+
+def check_long_rows_sens(be, N, K, report=None):
+    """the same through plain `mc_fidelity_sens` on a draw tensor"""
+    ctrl = philox_ctrl(N)
+    draws = PHILOX_SIGMA * np.random.default_rng(8800 + N).standard_normal((ctrl.shape[0], K, N, 3))
+    res = be.mc_fidelity_sens(ctrl, draws, N, 0, N - 1)
+    assert_sens_teeth(res["sens"], ("long rows, draw tensor", N, K))
+    assert all(np.isnan(res[k][1]).all() for k in PHILOX_OUTPUTS)
+    _assert_mean_of_same_launch(res, draws, K, f"long rows, draw tensor, N = {N}, K = {K}", report)
+    gc.assert_same_bits(be.mc_fidelity_sens(ctrl, draws, N, 0, N - 1, want=("mean",)), res, ("long rows", "mean alone"), ("mean",))
+
+
+def check_far_offsets_sens_philox(be, N, K=130, worst=None):
+    """grad_checks.check_far_offsets_grad_philox for the sensitivity entry"""
+    ctrl = philox_ctrl(N)
+    for offset in (gc.wrap_offset(N), gc.FAR_OFFSET):
+        for (a, b) in gc.grad_pairs(N)[:2]:
+            what = ("far offset", N, a, b, offset)
+            draws, Fw, Sw = reference_on_host_draws(ctrl, K, N, a, b, offset)
+            assert_sens_teeth(Sw, what)
+            got = _fused(be, ctrl, K, N, a, b, offset)
+            gc.assert_same_bits(got, _two_kernels(be, ctrl, K, N, a, b, offset), what, PHILOX_OUTPUTS)
+            out = _compare_with_reference(got, ctrl, draws, Fw, Sw, N, what)
+            if worst is not None:
+                worst.add(("far offset", N), out)

@@ -3,9 +3,11 @@ second-moment sums behind the gradient of the variance - on the device: BIT-IDEN
 `mc_fidelity_grad`) in fid, grad and mean at every pass schedule (one pass: N <= 9; several: N = 10, 11, 12), both parities of
 the first element, tile boundaries, both draw modes and per-row sigma; the moment sums against host sums of the same launch's
 per-sample outputs; everything against an independent reference (host-regenerated draws, eigh); and through
-`scripts/robust_lbfgs.py`.  Shapes are the smallest that reach those paths: C = 3 rows (one NaN, one with a negative time entry),
-K = 130 = tiles of 64, 64 and 2 samples.  ROBCHAR_GRAD_FORCED_GENERAL=1 announces a -DRC_GRAD_FORCE_GENERAL=1 variant build
-(scripts/build_variant.sh), in which every tile takes the sweep-cap fallback."""
+`scripts/robust_lbfgs.py`.  With static Hamiltonian terms (XXZ diagonal, non-unit couplings of both signs), rows of more than 64
+tiles in the row-mean kernel and stream offsets past 2^33: the checks of grad_checks.py (`check_*_grad_philox`).  Shapes are the
+smallest that reach those paths: C = 3 rows (one NaN, one with a negative time entry), K = 130 = tiles of 64, 64 and 2 samples.
+ROBCHAR_GRAD_FORCED_GENERAL=1 announces a -DRC_GRAD_FORCE_GENERAL=1 variant build (scripts/build_variant.sh), in which every
+tile takes the sweep-cap fallback."""
 import importlib
 import itertools
 import os
@@ -29,37 +31,26 @@ KEYS = ("fid", "grad", "mean")
 ALL = KEYS + ("moment",)
 
 
-def ctrl_rows(N, C=3, nan_row=1, neg_row=2):
-    """delocalised rows (the gradients have teeth there), one of them NaN, one with a negative time entry"""
-    ctrl = cc.deloc_ctrl(np.random.default_rng(9300 + N), C, N, 0.5)
-    if neg_row is not None:
-        ctrl[neg_row, N] = -ctrl[neg_row, N]
-    if nan_row is not None:
-        ctrl[nan_row, N // 2] = np.nan
-    return ctrl
+ctrl_rows = gc.philox_ctrl      # delocalised rows (the gradients have teeth there), one of them NaN, one with a negative time entry
 
 
-def fused(be, ctrl, K, N, a, b, offset=0, sigma=SIGMA, seed=SEED, shared=False, want=ALL):
+def fused(be, ctrl, K, N, a, b, offset=0, sigma=SIGMA, seed=SEED, shared=False, want=ALL, h0_diag=None, h0_offdiag=None):
     import torch
     dev = be.compute_device()
     if not isinstance(sigma, float):
         sigma = torch.from_numpy(np.asarray(sigma, dtype=np.float64)).to(dev)
     res = be.mc_fidelity_grad_philox(torch.from_numpy(ctrl).to(dev), K, N, a, b, seed, offset=offset, sigma=sigma, shared=shared,
-                                     want=want)
+                                     h0_diag=h0_diag, h0_offdiag=h0_offdiag, want=want)
     return {k: v.cpu().numpy() for k, v in res.items()}
 
 
-def two_kernels(be, ctrl, K, N, a, b, offset=0, sigma=SIGMA, seed=SEED, shared=False):
+def two_kernels(be, ctrl, K, N, a, b, offset=0, sigma=SIGMA, seed=SEED, shared=False, h0_diag=None, h0_offdiag=None):
     draws = be.philox_normal((1 if shared else ctrl.shape[0], K, N, 3), seed, scale=sigma, offset=offset)
-    return be.mc_fidelity_grad(ctrl, draws, N, a, b)
+    return be.mc_fidelity_grad(ctrl, draws, N, a, b, h0_diag=h0_diag, h0_offdiag=h0_offdiag)
 
 
 def assert_same_bits(got, want, what, keys=KEYS):
-    for k in keys:
-        assert got[k].shape == want[k].shape, (what, k)
-        assert np.array_equal(got[k], want[k], equal_nan=True), (
-            what, k, "differs in", int((~((got[k] == want[k]) | (np.isnan(got[k]) & np.isnan(want[k])))).sum()), "entries, max |diff|",
-            float(np.nanmax(np.abs(got[k] - want[k]))))
+    gc.assert_same_bits(got, want, what, keys)
 
 
 def check_identity(be, N, K=130, offsets=(0, 7)):
@@ -125,8 +116,7 @@ def test_per_row_sigma(be, N, shared):
         assert not (got["fid"][1] == got["fid"][1, 0]).all()
 
 
-def host_moments(res):
-    return np.concatenate([(res["fid"] ** 2).mean(axis=1)[:, None], (res["fid"][..., None] * res["grad"]).mean(axis=1)], axis=1)
+host_moments = gc.host_moments
 
 
 @pytest.mark.parametrize("N", (7, 11))
@@ -186,23 +176,120 @@ def test_independent_reference(be, N, sigma):
         mw = np.concatenate([Fw.mean(axis=1)[:, None], Gw.mean(axis=1)], axis=1)
         mb = np.concatenate([np.full((C, 1), gc.TOL), bars.max(axis=1)], axis=1)
         gc.compare_grad(got["mean"], mw, mb, ("fused", N, a, b, "mean"))
-        # the reference's own moments and the teeth guard
-        var_w, std_w = np.var(Fw[ok], axis=1), np.std(Fw[ok], axis=1)
-        gvar_w = 2.0 * ((Fw[ok][..., None] * Gw[ok]).mean(axis=1) - Fw[ok].mean(axis=1)[:, None] * Gw[ok].mean(axis=1))
-        gvar_bound = 4.0 * (gc.TOL * np.abs(Gw[ok]).max(axis=1) + bars[ok].max(axis=1))
-        assert std_w.min() >= 0.01, (N, a, b, sigma, std_w)
-        assert (np.abs(gvar_w) >= 100.0 * gvar_bound).all(), (N, a, b, sigma, float((np.abs(gvar_w) / gvar_bound).min()))
         nm = noise.structured_perturbation(Nspin=N, inspin=a, outspin=b, noise=sigma)
         m = nm.fidelity_moments_philox(ctrl, K, SEED, offset=offset)
-        assert all(np.isnan(v[1]).all() for v in m.values())
         assert np.array_equal(m["fav"][ok], got["mean"][ok, 0]) and np.array_equal(m["grad_fav"][ok], got["mean"][ok, 1:])
-        ev, eg = np.abs(m["var"][ok] - var_w).max(), (np.abs(m["grad_var"][ok] - gvar_w) / gvar_bound).max()
+        ev, eg, smin = assert_moments_match(m, Fw, Gw, bars, (N, a, b, sigma))
         print(f"fused gradient kernel, N = {N}, {a} -> {b}, sigma = {sigma}: worst |grad error| {e[0]:.2e} ({e[1]:.2e} of its bar); "
-              f"|var error| {ev:.2e}, grad_var error {eg:.2e} of its bound; smallest std {std_w.min():.3f}")
-        assert ev < 4.0 * gc.TOL
-        assert eg < 1.0
-        assert (np.abs(m["grad_std"][ok] * 2.0 * m["std"][ok][:, None] - m["grad_var"][ok]) <= 1e-14 * np.abs(m["grad_var"][ok])).all()
-        assert np.abs(m["std"][ok] - std_w).max() < 4.0 * gc.TOL / std_w.min()          # |sqrt u - sqrt v| <= |u - v| / sqrt v
+              f"|var error| {ev:.2e}, grad_var error {eg:.2e} of its bound; smallest std {smin:.3f}")
+
+
+def assert_moments_match(m, Fw, Gw, bars, what, ok=(0, 2)):
+    """`fidelity_moments_philox` against the reference's own moments, bounds and teeth as in the docstring of
+    test_independent_reference; returns (|var error|, grad_var error / its bound, smallest std)"""
+    ok = list(ok)
+    var_w, std_w = np.var(Fw[ok], axis=1), np.std(Fw[ok], axis=1)
+    gvar_w = 2.0 * ((Fw[ok][..., None] * Gw[ok]).mean(axis=1) - Fw[ok].mean(axis=1)[:, None] * Gw[ok].mean(axis=1))
+    gvar_bound = 4.0 * (gc.TOL * np.abs(Gw[ok]).max(axis=1) + bars[ok].max(axis=1))
+    assert std_w.min() >= 0.01, (what, std_w)
+    assert (np.abs(gvar_w) >= 100.0 * gvar_bound).all(), (what, float((np.abs(gvar_w) / gvar_bound).min()))
+    assert all(np.isnan(v[1]).all() for v in m.values())
+    ev, eg = np.abs(m["var"][ok] - var_w).max(), (np.abs(m["grad_var"][ok] - gvar_w) / gvar_bound).max()
+    assert ev < 4.0 * gc.TOL, (what, "var", ev)
+    assert eg < 1.0, (what, "grad_var", eg)
+    assert (np.abs(m["grad_std"][ok] * 2.0 * m["std"][ok][:, None] - m["grad_var"][ok]) <= 1e-14 * np.abs(m["grad_var"][ok])).all()
+    assert np.abs(m["std"][ok] - std_w).max() < 4.0 * gc.TOL / std_w.min()          # |sqrt u - sqrt v| <= |u - v| / sqrt v
+    return float(ev), float(eg), float(std_w.min())
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# static Hamiltonian terms, rows of more than 64 tiles, far stream offsets
+# ---------------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("N", (2, 3, 7, 10, 12))
+def test_static_terms_bit_identity(be, N):
+    """h0_diag (XXZ) and non-unit h0_offdiag of both signs reach the kernel that generates its draws exactly as they reach the
+    two-kernel route: every case of grad_checks.static_cases, every pair, offsets 0 and 7, both draw modes.  (The general-tile
+    counter as in test_bit_identity_with_the_two_kernel_route.)"""
+    assert gc.PHILOX_SEED == SEED and gc.PHILOX_SIGMA == SIGMA
+    be.grad_general_tiles(reset=True)
+    gc.check_static_grad_philox(be, N, reference=False)
+    tiles = be.grad_general_tiles(reset=True)
+    assert (tiles > 0) if FORCED else (tiles == 0), tiles
+
+
+@pytest.mark.parametrize("N", (5, 10))
+def test_static_terms_independent_reference(be, N):
+    """the same cases against grad_eigh with the same terms on host-regenerated draws"""
+    worst = gc.Worst()
+    gc.check_static_grad_philox(be, N, identity=False, worst=worst)
+    print(f"static terms, generated draws: {worst}")
+
+
+@pytest.mark.parametrize("N", (5, 10))
+def test_static_terms_through_the_noise_model(be, N):
+    """`structured_perturbation` whose HH carries the XXZ diagonal and the non-unit real couplings: `fidelity_moments_philox` gives
+    the bits of the backend call with those h0_* and matches the reference's moments (bounds of test_independent_reference); a
+    static imaginary coupling is refused.  At the default sigma = 0.05, on the rows of controller seed 9400 + N: on those of
+    9300 + N the reference's std of one row (N = 10, 0 -> 9: 0.0098) is under the 0.01 that the moment comparison wants of it; on
+    these the smallest is 0.030 (N = 5) and 0.018 (N = 10)."""
+    noise = importlib.import_module("code-robchar_amd.noise")
+    K, offset, ok, sigma = 130, 7, [0, 2], SIGMA
+    ctrl = ctrl_rows(N, seed=9400 + N)
+    h0d, h0o = gc.static_terms(N, "both")
+    for (a, b) in ((0, N - 1), (min(1, N - 1), N // 2)):
+        nm = noise.structured_perturbation(Nspin=N, inspin=a, outspin=b, noise=sigma)
+        nm.HH = gc.static_hh(N, "both")
+        for shared in (False, True):
+            draws, Fw, Gw = gc.reference_on_host_draws(ctrl, K, N, a, b, offset, shared, h0d, h0o, sigma=sigma)
+            gc.assert_static_teeth(Fw, gc.grad_eigh(ctrl, draws, N, a, b)[0], ("noise model", N, a, b))
+            m = nm.fidelity_moments_philox(ctrl, K, SEED, offset=offset, shared=shared)
+            got = fused(be, ctrl, K, N, a, b, offset, shared=shared, sigma=sigma, want=("mean", "moment"), h0_diag=h0d, h0_offdiag=h0o)
+            assert np.array_equal(m["fav"][ok], got["mean"][ok, 0]) and np.array_equal(m["grad_fav"][ok], got["mean"][ok, 1:])
+            want = noise.moments_from_sums(got["mean"], got["moment"])
+            assert all(np.array_equal(m[k], want[k], equal_nan=True) for k in want)
+            bars = gc.grad_bars(ctrl, draws, N, h0d, h0o)
+            ev, eg, smin = assert_moments_match(m, Fw, Gw, bars, ("noise model", N, a, b, shared))
+            print(f"noise model with static terms, N = {N}, {a} -> {b}, shared = {shared}: |var error| {ev:.2e} (bound {4 * gc.TOL:.1e}), "
+                  f"grad_var error {eg:.2e} of its bound; smallest std {smin:.3f}")
+        nm.HH[1, 0] += 0.1j
+        nm.HH[0, 1] -= 0.1j
+        with pytest.raises(NotImplementedError, match="real static couplings"):
+            nm.fidelity_moments_philox(ctrl, K, SEED, offset=offset)
+
+
+@pytest.mark.parametrize("K", (4096, 4097, 8193))
+@pytest.mark.parametrize("N", (7, 11))
+def test_long_rows(be, N, K):
+    """64, 65 and 129 tiles per row: the strided loop of the row-mean kernel takes one, two and three steps (one and three QL
+    passes in the gradient kernel)"""
+    gc.check_long_rows_grad_philox(be, N, K, report=print)
+
+
+def test_long_rows_moments_against_the_reference(be):
+    """N = 5, K = 4097 (65 tiles): `fidelity_moments_philox` against the reference's own moments, bounds and teeth of
+    test_independent_reference"""
+    noise = importlib.import_module("code-robchar_amd.noise")
+    N, K, offset = 5, 4097, 7
+    ctrl = ctrl_rows(N)
+    for (a, b) in ((0, N - 1), (min(1, N - 1), N // 2)):
+        draws, Fw, Gw = gc.reference_on_host_draws(ctrl, K, N, a, b, offset, False)
+        gc.assert_grad_teeth(Gw, ("long rows, reference", N, a, b))
+        nm = noise.structured_perturbation(Nspin=N, inspin=a, outspin=b, noise=SIGMA)
+        m = nm.fidelity_moments_philox(ctrl, K, SEED, offset=offset)
+        ev, eg, smin = assert_moments_match(m, Fw, Gw, gc.grad_bars(ctrl, draws, N), ("long rows", N, a, b))
+        print(f"moments over 65 tiles, N = {N}, {a} -> {b}: |var error| {ev:.2e} (bound {4 * gc.TOL:.1e}), grad_var error {eg:.2e} of "
+              f"its bound; smallest std {smin:.3f}")
+
+
+@pytest.mark.parametrize("N", (7, 11))
+def test_far_offsets(be, N):
+    """the pair counter's low word wraps inside the first tile (offset 2^33 - 32 * 3 N - 1), and a counter with a non-zero high
+    word from the start"""
+    worst = gc.Worst()
+    gc.check_far_offsets_grad_philox(be, N, worst=worst)
+    print(f"far stream offsets, generated draws: {worst}")
 
 
 def test_unsupported_and_rejected(be):

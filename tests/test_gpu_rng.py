@@ -38,6 +38,15 @@ def test_philox_device_draws(be):
     assert np.abs(got - want).max() < 1e-15
     part = be.philox_normal((1000,), seed, scale=0.05, offset=7 + 5000)
     assert np.array_equal(part, got[5000:6000])
+    # across element 2^33, where the low word of the pair counter (element >> 1) wraps and the high word becomes 1
+    wrap, n = 2 ** 33, 4099
+    got = be.philox_normal((n,), seed, scale=0.05, offset=wrap - 2001)
+    want = philox_host.philox_normal(seed, wrap - 2001, n, 0.05)
+    assert np.abs(got - want).max() < 1e-15
+    assert np.abs(want[2001:] - philox_host.philox_normal(seed, 0, n - 2001, 0.05)).max() > 0.05      # not the stream's start again
+    for start in (wrap - 500, wrap - 1, wrap, wrap + 1):
+        part = be.philox_normal((1000,), seed, scale=0.05, offset=start)
+        assert np.array_equal(part, got[start - (wrap - 2001):][:1000]), start
     big = be.philox_normal((4_000_000,), 99, as_torch=True)
     assert abs(float(big.mean())) < 3e-3 and abs(float(big.std()) - 1) < 3e-3
     assert abs(float((big ** 4).mean()) - 3) < 5e-2
@@ -211,6 +220,50 @@ def test_philox_draws_inside_the_fidelity_kernel(be, N):
                 w = be.mc_fidelity(ct[c:c + 1], be.philox_normal((1, K, N, 3), seed, scale=float(sig[c]), offset=off + c * K * N * 3,
                                                                 device=dev, as_torch=True), N, a, b)
                 assert torch.equal(torch.nan_to_num(got_r[c:c + 1]), torch.nan_to_num(w)), (N, c)
+
+
+@pytest.mark.parametrize("N", (2, 5, 10, 13, 14, 16))
+def test_philox_draws_inside_the_fidelity_kernel_with_static_terms(be, N):
+    """The fused fidelity kernel with h0_diag (XXZ) and non-unit h0_offdiag of both signs (grad_checks.static_cases) under random
+    draws, on delocalised controllers with a NaN row: bit-identical to `mc_fidelity` on `philox_normal` draws with the same terms,
+    inside chain_checks.compare of the oracle on host-regenerated draws; at offset 0 and at an odd offset where the pair counter's
+    low word wraps inside the first tile; one scale per row once.  Guards on the reference alone: the terms move F, median F >= 1e-2."""
+    import torch
+    import chain_checks as cc
+    import grad_checks as gc
+    dev = torch.device("cuda", torch.cuda.current_device())
+    C, seed = 3, 0x5EED000B
+    ctrl = cc.deloc_ctrl(np.random.default_rng(9500 + N), C, N, 0.5)
+    ctrl[1, N // 2] = np.nan
+    ct = torch.from_numpy(ctrl).to(dev)
+    worst = cc.Worst()
+    for case in gc.static_cases(N):
+        h0d, h0o = gc.static_terms(N, case)
+        for (a, b) in ((0, N - 1), (N // 2, 0)):
+            for (K, off) in ((130, 0), (65, gc.wrap_offset(N))):
+                what = (N, case, a, b, K, off)
+                host = philox_host.philox_normal(seed, off, C * K * N * 3, 0.05).reshape(C, K, N, 3)
+                ref = orc.fidelity_eigh(ctrl, host, N, a, b, h0_diag=h0d, h0_offdiag=h0o)
+                gc.assert_static_teeth(ref, orc.fidelity_eigh(ctrl, host, N, a, b), what)
+                assert np.nanmedian(ref) >= 1e-2, (what, float(np.nanmedian(ref)))
+                draws = be.philox_normal((C, K, N, 3), seed, scale=0.05, offset=off, device=dev, as_torch=True)
+                want = be.mc_fidelity(ct, draws, N, a, b, h0_diag=h0d, h0_offdiag=h0o)
+                got = be.mc_fidelity_philox(ct, K, N, a, b, seed, offset=off, sigma=0.05, h0_diag=h0d, h0_offdiag=h0o)
+                assert torch.isnan(got[1]).all() and torch.equal(torch.isnan(got), torch.isnan(want)), what
+                assert torch.equal(torch.nan_to_num(got), torch.nan_to_num(want)), what
+                worst.add(case, cc.compare(got.cpu().numpy(), ref, what))
+    # one scale per controller row, with both static terms
+    a, b, K, off = 0, N - 1, 130, 7
+    sig = np.array([0.1, 0.05, 0.02])
+    got_r = be.mc_fidelity_philox(ct, K, N, a, b, seed, offset=off, sigma=torch.from_numpy(sig).to(dev), h0_diag=h0d, h0_offdiag=h0o)
+    for c in (0, 2):
+        w = be.mc_fidelity(ct[c:c + 1], be.philox_normal((1, K, N, 3), seed, scale=float(sig[c]), offset=off + c * K * N * 3, device=dev,
+                                                        as_torch=True), N, a, b, h0_diag=h0d, h0_offdiag=h0o)
+        assert torch.equal(got_r[c:c + 1], w), (N, "row", c)
+    host = philox_host.philox_normal(seed, off, C * K * N * 3, 1.0).reshape(C, K, N, 3) * sig[:, None, None, None]
+    ref = orc.fidelity_eigh(ctrl, host, N, a, b, h0_diag=h0d, h0_offdiag=h0o)
+    worst.add("per-row sigma", cc.compare(got_r.cpu().numpy(), ref, (N, "rows")))
+    print(f"fused fidelity kernel with static terms, N = {N}: {worst} (bars: abs {cc.TOL:.0e}, rel {cc.REL:.0e})")
 
 
 @pytest.mark.parametrize("N", [14, 15, 16])

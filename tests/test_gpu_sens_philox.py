@@ -3,8 +3,10 @@ device: BIT-IDENTICAL to the two-kernel route (`philox_normal` + `mc_fidelity_se
 schedule (one pass: N <= 9; 3 / 4 / 6 passes: N = 10 / 11 / 12), both pair parities of the first element, tile boundaries
 and per-row sigma; against an independent reference (host-regenerated draws, eigh); and through the product surface
 `MCDataSim.get_sensitivity_dict`.  Shapes are the smallest that reach those paths: C = 3 rows (one NaN), K = 130 = tiles of
-64, 64 and 2 samples.  ROBCHAR_GRAD_FORCED_GENERAL=1 announces a -DRC_GRAD_FORCE_GENERAL=1 variant build (scripts/build_variant.sh),
-in which every tile takes the sweep-cap fallback: run the bit-identity test for N = 7 and 10 on it."""
+64, 64 and 2 samples.  With static Hamiltonian terms, an exactly cut bond, rows of more than 64 tiles in the row-mean kernel and
+stream offsets past 2^33: the checks of sens_checks.py (`check_*_sens_philox`).  ROBCHAR_GRAD_FORCED_GENERAL=1 announces a
+-DRC_GRAD_FORCE_GENERAL=1 variant build (scripts/build_variant.sh), in which every tile takes the sweep-cap fallback: run the
+bit-identity test for N = 7 and 10 on it."""
 import importlib
 import json
 import os
@@ -26,34 +28,26 @@ IDENTITY_N = (2, 3, 7, 9, 10, 11, 12)
 KEYS = ("fid", "sens", "mean")
 
 
-def ctrl_rows(N, C=3, nan_row=1):
-    """delocalised rows (the sensitivities have teeth there), one of them NaN"""
-    ctrl = cc.deloc_ctrl(np.random.default_rng(9100 + N), C, N, 0.5)
-    if nan_row is not None:
-        ctrl[nan_row, N // 2] = np.nan
-    return ctrl
+ctrl_rows = sc.philox_ctrl      # delocalised rows (the sensitivities have teeth there), one of them NaN
 
 
-def fused(be, ctrl, K, N, a, b, offset=0, sigma=SIGMA, seed=SEED, want=KEYS):
+def fused(be, ctrl, K, N, a, b, offset=0, sigma=SIGMA, seed=SEED, want=KEYS, h0_diag=None, h0_offdiag=None):
     import torch
     dev = be.compute_device()
     if not isinstance(sigma, float):
         sigma = torch.from_numpy(np.asarray(sigma, dtype=np.float64)).to(dev)
-    res = be.mc_fidelity_sens_philox(torch.from_numpy(ctrl).to(dev), K, N, a, b, seed, offset=offset, sigma=sigma, want=want)
+    res = be.mc_fidelity_sens_philox(torch.from_numpy(ctrl).to(dev), K, N, a, b, seed, offset=offset, sigma=sigma, h0_diag=h0_diag,
+                                     h0_offdiag=h0_offdiag, want=want)
     return {k: v.cpu().numpy() for k, v in res.items()}
 
 
-def two_kernels(be, ctrl, K, N, a, b, offset=0, sigma=SIGMA, seed=SEED):
+def two_kernels(be, ctrl, K, N, a, b, offset=0, sigma=SIGMA, seed=SEED, h0_diag=None, h0_offdiag=None):
     draws = be.philox_normal((ctrl.shape[0], K, N, 3), seed, scale=sigma, offset=offset)
-    return be.mc_fidelity_sens(ctrl, draws, N, a, b)
+    return be.mc_fidelity_sens(ctrl, draws, N, a, b, h0_diag=h0_diag, h0_offdiag=h0_offdiag)
 
 
 def assert_same_bits(got, want, what):
-    for k in want:
-        assert got[k].shape == want[k].shape, (what, k)
-        assert np.array_equal(got[k], want[k], equal_nan=True), (
-            what, k, "differs in", int((~((got[k] == want[k]) | (np.isnan(got[k]) & np.isnan(want[k])))).sum()), "entries, max |diff|",
-            float(np.nanmax(np.abs(got[k] - want[k]))))
+    gc.assert_same_bits(got, want, what, tuple(want))
 
 
 def check_identity(be, N, K=130, offsets=(0, 7)):
@@ -115,6 +109,89 @@ def test_independent_reference(be, N):
         m = sc.compare_sens(got["mean"], sc.mean_of(Fw, draws, Sw), sc.mean_bars(bars, rbars), ("fused", N, a, b, "mean"))
         print(f"fused sensitivity kernel, N = {N}, {a} -> {b}: worst |sens error| {e[0]:.2e} ({e[1]:.2e} of its bar), "
               f"mean {m[0]:.2e} ({m[1]:.2e})")
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# static Hamiltonian terms, an exactly cut bond, rows of more than 64 tiles, far stream offsets
+# ---------------------------------------------------------------------------------------------------------------------------
+
+
+@pytest.mark.parametrize("N", (2, 3, 7, 10, 12))
+def test_static_terms_bit_identity(be, N):
+    """h0_diag (XXZ) and non-unit h0_offdiag of both signs - the kernel differentiates through re_i = h0_offdiag[i - 1] + g1_i -
+    reach the kernel that generates its draws exactly as they reach the two-kernel route.  (The general-tile counter as in
+    test_bit_identity_with_the_two_kernel_route.)"""
+    assert sc.PHILOX_SEED == SEED and sc.PHILOX_SIGMA == SIGMA
+    be.sens_general_tiles(reset=True)
+    sc.check_static_sens_philox(be, N, reference=False)
+    tiles = be.sens_general_tiles(reset=True)
+    assert (tiles > 0) if FORCED else (tiles == 0), tiles
+
+
+@pytest.mark.parametrize("N", (5, 10))
+def test_static_terms_independent_reference(be, N):
+    """the same cases against sens_eigh with the same terms on host-regenerated draws"""
+    worst = gc.Worst()
+    sc.check_static_sens_philox(be, N, identity=False, worst=worst)
+    print(f"static terms, generated draws: {worst}")
+
+
+@pytest.mark.parametrize("N", (5, 10))
+def test_static_terms_through_the_noise_model(be, N):
+    """`structured_perturbation` whose HH carries the XXZ diagonal and the non-unit real couplings: `noise_sensitivity_philox` gives
+    the bits of the backend call with those h0_* and sits inside the bars of the reference (as test_independent_reference); a
+    static imaginary coupling is refused."""
+    noise = importlib.import_module("code-robchar_amd.noise")
+    K, offset, ok = 130, 7, [0, 2]
+    ctrl = ctrl_rows(N)
+    h0d, h0o = gc.static_terms(N, "both")
+    for (a, b) in ((0, N - 1), (min(1, N - 1), N // 2)):
+        nm = noise.structured_perturbation(Nspin=N, inspin=a, outspin=b, noise=SIGMA)
+        nm.HH = gc.static_hh(N, "both")
+        draws, Fw, Sw = sc.reference_on_host_draws(ctrl, K, N, a, b, offset, h0d, h0o)
+        gc.assert_static_teeth(Fw, sc.sens_eigh(ctrl, draws, N, a, b)[0], ("noise model", N, a, b))
+        sc.assert_sens_teeth(Sw, ("noise model", N, a, b))
+        t = nm.noise_sensitivity_philox(ctrl, K, SEED, offset=offset)
+        mean = fused(be, ctrl, K, N, a, b, offset, want=("mean",), h0_diag=h0d, h0_offdiag=h0o)["mean"]
+        assert np.isnan(mean[1]).all() and all(np.isnan(v[1]).all() for v in t.values())
+        assert np.array_equal(t["fav"][ok], mean[ok, 0]) and np.array_equal(t["dfav_dlogsigma"][ok], mean[ok, 1])
+        assert np.array_equal(t["direction"][ok], mean[ok, 2:].reshape(-1, N, 3))
+        bars, rbars = sc.sens_bars(ctrl, draws, N)
+        packed = np.concatenate([t["fav"][:, None], t["dfav_dlogsigma"][:, None], t["direction"].reshape(len(ctrl), -1)], axis=1)
+        e = sc.compare_sens(packed, sc.mean_of(Fw, draws, Sw), sc.mean_bars(bars, rbars), ("noise model", N, a, b, "mean"))
+        print(f"noise model with static terms, N = {N}, {a} -> {b}: worst |mean error| {e[0]:.2e} ({e[1]:.2e} of its bar)")
+        nm.HH[1, 0] += 0.1j
+        nm.HH[0, 1] -= 0.1j
+        with pytest.raises(NotImplementedError, match="real static couplings"):
+            nm.noise_sensitivity_philox(ctrl, K, SEED, offset=offset)
+
+
+@pytest.mark.parametrize("N", (3, 7, 11))
+def test_cut_bond(be, N):
+    """a sigma = 0 row over a bond whose h0_offdiag is 0: r_i = 0 in every sample with the draws generated in the kernel"""
+    worst = gc.Worst()
+    sc.check_cut_bond_sens_philox(be, N, worst=worst)
+    print(f"cut bond, generated draws: {worst}")
+
+
+@pytest.mark.parametrize("K", (4096, 4097, 8193))
+@pytest.mark.parametrize("N", (7, 10))
+def test_long_rows(be, N, K):
+    """64, 65 and 129 tiles per row of 3 N + 2 means: the strided loop of the row-mean kernel takes one, two and three steps"""
+    sc.check_long_rows_sens_philox(be, N, K, report=print)
+
+
+def test_long_rows_from_a_draw_tensor(be):
+    sc.check_long_rows_sens(be, 7, 8193, report=print)
+
+
+@pytest.mark.parametrize("N", (7, 11))
+def test_far_offsets(be, N):
+    """the pair counter's low word wraps inside the first tile (offset 2^33 - 32 * 3 N - 1), and a counter with a non-zero high
+    word from the start"""
+    worst = gc.Worst()
+    sc.check_far_offsets_sens_philox(be, N, worst=worst)
+    print(f"far stream offsets, generated draws: {worst}")
 
 
 def test_output_subsets_and_side_stream(be):

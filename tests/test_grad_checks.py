@@ -7,7 +7,7 @@ import pytest
 import chain_checks as cc
 import grad_checks as gc
 
-BROKEN = ("zeros", "time_sign", "reversed", "gamma_diag")
+BROKEN = ("zeros", "time_sign", "reversed", "gamma_diag", "no_h0_diag", "no_h0_offdiag")
 
 
 @pytest.mark.parametrize("N", [2, 5, 7])
@@ -31,6 +31,51 @@ def test_deloc_check_fails_on_a_broken_gradient(broken):
 def test_closed_form_check_fails_on_a_broken_gradient(broken):
     with pytest.raises(AssertionError):
         gc.check_closed_form_grad(gc.StandIn(broken), 7)
+
+
+@pytest.mark.parametrize("N", [2, 5])
+def test_generated_draws_checks_pass_on_the_stand_in(N):
+    be = gc.StandIn()
+    worst = gc.Worst()
+    gc.check_static_grad_philox(be, N, worst=worst)
+    gc.check_far_offsets_grad_philox(be, N, worst=worst)
+    for K in (4096, 4097, 8193):
+        gc.check_long_rows_grad_philox(be, N, K)
+    assert "static" in str(worst) and "far offset" in str(worst)
+
+
+@pytest.mark.parametrize("N", [2, 3, 5, 7, 9, 10, 12])
+def test_static_cases_have_teeth_for_every_n(N):
+    """the guards of check_static_grad_philox (the static terms move F, the gradient is not tiny) hold on the reference"""
+    gc.check_static_grad_philox(gc.StandIn(), N, identity=False, reference=False)
+
+
+@pytest.mark.parametrize("broken", ("no_h0_diag", "no_h0_offdiag", "philox_no_h0_offdiag"))
+def test_static_reference_check_fails_on_a_dropped_static_term(broken):
+    with pytest.raises(AssertionError, match="static") as e:
+        gc.check_static_grad_philox(gc.StandIn(broken), 5, identity=False)
+    print(broken, "->", e.value)
+
+
+def test_static_identity_check_fails_when_only_the_generated_draws_route_drops_the_couplings():
+    with pytest.raises(AssertionError, match="differs in") as e:
+        gc.check_static_grad_philox(gc.StandIn("philox_no_h0_offdiag"), 5, reference=False)
+    print(e.value)
+    gc.check_static_grad_philox(gc.StandIn("no_h0_offdiag"), 5, reference=False)      # both routes wrong alike: the reference's job
+
+
+def test_far_offset_check_fails_on_a_lost_counter_carry():
+    with pytest.raises(AssertionError, match="far offset") as e:
+        gc.check_far_offsets_grad_philox(gc.StandIn("lost_carry"), 5)
+    print(e.value)
+
+
+@pytest.mark.parametrize("K", (4097, 8193))
+def test_long_rows_check_fails_on_row_sums_that_stop_after_64_tiles(K):
+    with pytest.raises(AssertionError, match="long rows") as e:
+        gc.check_long_rows_grad_philox(gc.StandIn("mean_64_tiles"), 5, K)
+    print(e.value)
+    gc.check_long_rows_grad_philox(gc.StandIn("mean_64_tiles"), 5, 4096)              # every lane has one tile: nothing to lose
 
 
 def test_hard_inputs_check_fails_on_a_dropped_time_sign():

@@ -69,3 +69,68 @@ def test_reference_has_teeth_for_every_n(N):
 def test_broken_stand_ins_fail(broken):
     with pytest.raises(AssertionError):
         _all_checks(sc.StandIn(broken), 5)
+
+
+@pytest.mark.parametrize("N", [3, 5])
+def test_generated_draws_checks_pass_on_the_stand_in(N):
+    be = sc.StandIn()
+    worst = gc.Worst()
+    sc.check_static_sens_philox(be, N, worst=worst)
+    sc.check_cut_bond_sens_philox(be, N, worst=worst)
+    sc.check_far_offsets_sens_philox(be, N, worst=worst)
+    for K in (4096, 4097, 8193):
+        sc.check_long_rows_sens_philox(be, N, K)
+    sc.check_long_rows_sens(be, N, 4097)
+    assert all(k in str(worst) for k in ("static", "cut bond", "far offset"))
+
+
+@pytest.mark.parametrize("N", [2, 3, 5, 7, 10, 12])
+def test_static_cases_have_teeth(N):
+    """the reference-only guards of the static-term check hold at every N the GPU tests run it at"""
+    sc.check_static_sens_philox(sc.StandIn(), N, identity=False, reference=False)
+
+
+@pytest.mark.parametrize("N", [3, 7, 11])
+def test_cut_bond_check_passes_on_the_stand_in(N):
+    sc.check_cut_bond_sens_philox(sc.StandIn(), N)
+
+
+@pytest.mark.parametrize("broken", ("no_h0_diag", "no_h0_offdiag", "re_g1", "philox_no_h0_offdiag"))
+def test_static_reference_check_fails_on_wrong_static_terms(broken):
+    with pytest.raises(AssertionError, match="static") as e:
+        sc.check_static_sens_philox(sc.StandIn(broken), 5, identity=False)
+    print(broken, "->", e.value)
+
+
+def test_static_identity_check_fails_when_only_the_generated_draws_route_drops_the_couplings():
+    with pytest.raises(AssertionError, match="differs in") as e:
+        sc.check_static_sens_philox(sc.StandIn("philox_no_h0_offdiag"), 5, reference=False)
+    print(e.value)
+
+
+@pytest.mark.parametrize("broken", ("re_g1", "no_h0_offdiag", "no_phase"))
+def test_cut_bond_check_fails(broken):
+    """re = g1 at the cut bond of the sigma = 0 row is 0 / 0; without h0_offdiag the chain is not cut; dF/dr without re / r is 0 / 0"""
+    with pytest.raises(AssertionError, match="cut bond") as e:
+        sc.check_cut_bond_sens_philox(sc.StandIn(broken), 7)
+    print(broken, "->", e.value)
+
+
+def test_far_offset_check_fails_on_a_lost_counter_carry():
+    with pytest.raises(AssertionError, match="far offset") as e:
+        sc.check_far_offsets_sens_philox(sc.StandIn("lost_carry"), 5)
+    print(e.value)
+
+
+@pytest.mark.parametrize("K", (4097, 8193))
+def test_long_rows_check_fails_on_row_sums_that_stop_after_64_tiles(K):
+    with pytest.raises(AssertionError, match="long rows") as e:
+        sc.check_long_rows_sens_philox(sc.StandIn("mean_64_tiles"), 5, K)
+    print(e.value)
+    sc.check_long_rows_sens_philox(sc.StandIn("mean_64_tiles"), 5, 4096)
+
+
+def test_long_rows_check_fails_on_a_mean_divided_by_the_tiles():
+    with pytest.raises(AssertionError, match="long rows") as e:
+        sc.check_long_rows_sens(sc.StandIn("mean_by_tiles"), 5, 4097)
+    print(e.value)
