@@ -49,6 +49,7 @@
 #include "sort_core.h"
 #include "legacy_rng_core.h"
 #include "mt19937_jump_poly.h"
+#include "ws_plan.h"
 
 // The largest instantiations live in a second translation unit (robchar_large.hip) that compiles in parallel with this one:
 // chains of 17 .. 24 spins (general adjugate mode), rings of 11 .. 16 spins (mixed route + repair, all-fp64 route).  Each
@@ -193,6 +194,33 @@ bool is_device_ptr(const void* p) {
     }
     return attr.type == hipMemoryTypeDevice;
 }
+
+// The device workspace of one blocking call (caller holds the device's `mu`): the call declares its arrays in order - either
+// input and any output may be a host or a device pointer - and ws_plan.h derives the carving.  stage_in(): grows the workspace
+// to the plan's total, then copies the staged inputs in; ptr(): what the kernel is given; stage_out(): copies the staged outputs
+// back behind the launch and waits for the stream.
+struct Staging {
+    DeviceCtx* ctx = nullptr;
+    rcws::Plan plan;
+    int in(const void* p, size_t bytes) { return plan.in(p, bytes, is_device_ptr(p)); }
+    int out(void* p, size_t bytes, bool always = false) { return plan.out(p, bytes, p && !always && is_device_ptr(p), always); }
+    double* ptr(int slot) const { return (double*)plan.ptr(slot, ctx->ws); }
+    int stage_in() {
+        if (int rc = ensure_ws(ctx, plan.total)) return rc;
+        for (int i = 0; i < plan.n; ++i)
+            if (const rcws::Slot& s = plan.s[i]; s.input && s.staged)
+                RC_HIP_CHECK(hipMemcpyAsync(ptr(i), s.user, s.bytes, hipMemcpyHostToDevice, ctx->stream));
+        return RC_OK;
+    }
+    int stage_out() {
+        for (int i = 0; i < plan.n; ++i)
+            if (const rcws::Slot& s = plan.s[i]; !s.input && s.staged && s.user)
+                RC_HIP_CHECK(hipMemcpyAsync((void*)s.user, ptr(i), s.bytes, s.always ? hipMemcpyDefault : hipMemcpyDeviceToHost,
+                                            ctx->stream));
+        RC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return RC_OK;
+    }
+};
 
 // stream-ordered release of a hipMallocAsync block at scope exit
 struct StreamFree {
@@ -612,73 +640,76 @@ int enqueue_reduce(hipStream_t s, const double* fid, long long C, long long K, c
 // collective is needed for a host-resident result.
 constexpr size_t kShardChunkBytes = (size_t)4 << 30;
 
-struct ShardJob {
+// What one device's share of the sample space is computed from, common to the sharded entries and the RCCL entry: the call's
+// arguments, filled once per call, and - per share - `device`, its controllers [c0, c1) and the worker's result.
+struct ShareSpec {
     int device, kernel, N, in, out, ring;
     const double *h0d, *h0o, *ctrl, *draws;          // host; draws may be null (Philox)
     unsigned long long seed, offset;
     double sigma;
-    long long C, K, c0, c1;                          // this device owns controllers [c0, c1)
+    long long C, K, c0, c1;
     const double* thr;
     int nq;
     double eps;
-    double *rim1, *stdv, *minf, *q, *fid_out;        // host, FULL arrays ([3][C], [3][nq][C], [C][K]); may be null
     int rc = RC_OK;
     std::string err;
 };
 
+// Counter-based draws on a chain of <= 16 spins with the eigenvalue-only kernels: generated inside the fidelity kernel
+// (k_fidelity_philox.inc.h) - no draw tensor.  ONE predicate for this route and the Python layer's: rc_philox_fused_pays
+// (environment switch read per call); who sizes the buffers asks once and hands enqueue_share no draw buffer when it holds.
+bool philox_fused_route(const double* draws, int ring, int kernel, int N, int in, int out) {
+    return !draws && !ring && rc_philox_fused_pays(N, in, out) == 1 && (kernel == RC_KERNEL_AUTO || kernel == RC_KERNEL_TRIDIAG_ADJ);
+}
+
+// Controllers [a, a + cc) of `sp` on its device: their rows into `d_ctrl`, their fidelities into rows [0, cc) of `d_fid` - from
+// the host's draws or the Philox stream through `d_draw`, or (`d_draw` NULL: philox_fused_route) by the fused Philox kernel.
+// Enqueued on `st`; nothing waits.
+int enqueue_share(const ShareSpec& sp, long long a, long long cc, double* d_ctrl, double* d_draw, double* d_fid, hipStream_t st) {
+    const long long G = 3LL * sp.N, K = sp.K;
+    RC_HIP_CHECK(hipMemcpyAsync(d_ctrl, sp.ctrl + a * (sp.N + 1), (size_t)cc * (sp.N + 1) * sizeof(double), hipMemcpyHostToDevice, st));
+    // element ((c K + k) N + i) 3 + slot of the stream: independent of how the controllers are sharded
+    const unsigned long long first = sp.offset + (unsigned long long)(a * K * G);
+    if (!d_draw)
+        return rc_mc_fidelity_philox_f64_async(sp.device, st, sp.kernel, sp.N, sp.in, sp.out, sp.h0d, sp.h0o, d_ctrl, sp.seed, first,
+                                               sp.sigma, nullptr, cc, K, d_fid);
+    if (sp.draws) {
+        RC_HIP_CHECK(hipMemcpyAsync(d_draw, sp.draws + a * K * G, (size_t)cc * K * G * sizeof(double), hipMemcpyHostToDevice, st));
+    } else if (int rc = rc_draws_philox_f64_async(sp.device, st, sp.seed, first, cc * K * G, sp.sigma, d_draw)) {
+        return rc;
+    }
+    return enqueue_fidelity(st, sp.kernel, sp.N, sp.in, sp.out, sp.h0d, sp.h0o, sp.ring, d_ctrl, d_draw, -1, cc, K, d_fid);
+}
+
+struct ShardJob : ShareSpec {
+    double *rim1, *stdv, *minf, *q, *fid_out;        // host, FULL arrays ([3][C], [3][nq][C], [C][K]); may be null
+};
+
 int run_shard_locked(ShardJob* j) {
-    DeviceCtx* ctx = nullptr;
-    if (int rc = get_ctx(j->device, &ctx)) return rc;
+    Staging ws;
+    if (int rc = get_ctx(j->device, &ws.ctx)) return rc;
     const long long G = 3LL * j->N, K = j->K, Cl = j->c1 - j->c0;
     if (Cl <= 0 || K == 0) return RC_OK;
     const bool want_red = j->rim1 || j->stdv || j->minf || (j->q && j->nq);
-    // counter-based draws on a chain of <= 16 spins with the eigenvalue-only kernels: generated inside the fidelity kernel
-    // (k_fidelity_philox.inc.h) - no draw tensor, so a chunk is bounded by its fidelities only (K x 8 bytes per controller)
-    // (ONE predicate for this route and the Python layer's: rc_philox_fused_pays, environment switch read per call)
-    const bool fused = !j->draws && !j->ring && rc_philox_fused_pays(j->N, j->in, j->out) == 1 &&
-                       (j->kernel == RC_KERNEL_AUTO || j->kernel == RC_KERNEL_TRIDIAG_ADJ);
+    // a chunk is bounded by its draws; on the fused route by its fidelities only (K x 8 bytes per controller)
+    const bool fused = philox_fused_route(j->draws, j->ring, j->kernel, j->N, j->in, j->out);
     long long cc_max = (long long)(kShardChunkBytes / ((size_t)K * (fused ? 1 : G) * sizeof(double)));
     if (cc_max < 1) cc_max = 1;
     if (cc_max > Cl) cc_max = Cl;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t nb_ctrl = up((size_t)cc_max * (j->N + 1) * sizeof(double));
-    const size_t nb_draw = fused ? 0 : up((size_t)cc_max * K * G * sizeof(double));
-    const size_t nb_fid = up((size_t)cc_max * K * sizeof(double));
-    const size_t nb_c3 = up((size_t)3 * cc_max * sizeof(double));
-    const size_t nb_q = up((size_t)3 * (j->nq > 0 ? j->nq : 1) * cc_max * sizeof(double));
-    if (int rc = ensure_ws(ctx, nb_ctrl + nb_draw + nb_fid + 3 * nb_c3 + nb_q)) return rc;
-    char* w = (char*)ctx->ws;
-    double* d_ctrl = (double*)w; w += nb_ctrl;
-    double* d_draw = (double*)w; w += nb_draw;
-    double* d_fid = (double*)w;  w += nb_fid;
-    double* d_rim = (double*)w;  w += nb_c3;
-    double* d_std = (double*)w;  w += nb_c3;
-    double* d_min = (double*)w;  w += nb_c3;
-    double* d_q = (double*)w;
-    hipStream_t st = ctx->stream;
+    // planned once for cc_max controllers, reused by every chunk
+    const size_t nb_c3 = (size_t)3 * cc_max * sizeof(double);
+    const int s_ctrl = ws.plan.scratch((size_t)cc_max * (j->N + 1) * sizeof(double)),
+              s_draw = ws.plan.scratch(fused ? 0 : (size_t)cc_max * K * G * sizeof(double)),
+              s_fid = ws.plan.scratch((size_t)cc_max * K * sizeof(double)), s_rim = ws.plan.scratch(nb_c3),
+              s_std = ws.plan.scratch(nb_c3), s_min = ws.plan.scratch(nb_c3),
+              s_q = ws.plan.scratch(nb_c3 * (j->nq > 0 ? j->nq : 1));
+    if (int rc = ws.stage_in()) return rc;
+    double *d_ctrl = ws.ptr(s_ctrl), *d_draw = fused ? nullptr : ws.ptr(s_draw), *d_fid = ws.ptr(s_fid), *d_rim = ws.ptr(s_rim),
+           *d_std = ws.ptr(s_std), *d_min = ws.ptr(s_min), *d_q = ws.ptr(s_q);
+    hipStream_t st = ws.ctx->stream;
     for (long long a = j->c0; a < j->c1; a += cc_max) {
         const long long cc = (j->c1 - a < cc_max) ? (j->c1 - a) : cc_max;
-        RC_HIP_CHECK(hipMemcpyAsync(d_ctrl, j->ctrl + a * (j->N + 1), (size_t)cc * (j->N + 1) * sizeof(double),
-                                    hipMemcpyHostToDevice, st));
-        if (fused) {
-            // element ((c K + k) N + i) 3 + slot of the stream: independent of how the controllers are sharded
-            if (int rc = rc_mc_fidelity_philox_f64_async(j->device, st, j->kernel, j->N, j->in, j->out, j->h0d, j->h0o, d_ctrl,
-                                                         j->seed, j->offset + (unsigned long long)(a * K * G), j->sigma, nullptr,
-                                                         cc, K, d_fid))
-                return rc;
-        } else if (j->draws) {
-            RC_HIP_CHECK(hipMemcpyAsync(d_draw, j->draws + a * K * G, (size_t)cc * K * G * sizeof(double),
-                                        hipMemcpyHostToDevice, st));
-        } else {
-            // element ((c K + k) N + i) 3 + slot of the stream: independent of how the controllers are sharded
-            if (int rc = rc_draws_philox_f64_async(j->device, st, j->seed, j->offset + (unsigned long long)(a * K * G),
-                                                   cc * K * G, j->sigma, d_draw))
-                return rc;
-        }
-        if (!fused)
-            if (int rc = enqueue_fidelity(st, j->kernel, j->N, j->in, j->out, j->h0d, j->h0o, j->ring, d_ctrl, d_draw, -1, cc, K,
-                                          d_fid))
-                return rc;
+        if (int rc = enqueue_share(*j, a, cc, d_ctrl, d_draw, d_fid, st)) return rc;
         if (want_red) {
             if (int rc = enqueue_reduce(st, d_fid, cc, K, j->thr, j->nq, j->eps, j->rim1 ? d_rim : nullptr,
                                         j->stdv ? d_std : nullptr, j->minf ? d_min : nullptr,
@@ -1263,49 +1294,19 @@ int rccl_fail(int code, const char* what) {
 
 // One device's share of rc_mc_metrics_gathered_f64: controllers [c0, c1) -> fidelities into rows [0, c1 - c0) of `d_fid` (Cmax rows,
 // the rest zero) and their metric rows into `d_tab` ([NR][Cmax]).  Everything is enqueued on the device's stream; nothing waits.
-struct GatherJob {
-    int device, kernel, N, in, out, ring;
-    const double *h0d, *h0o, *ctrl, *draws;
-    unsigned long long seed, offset;
-    double sigma;
-    long long C, K, c0, c1, Cmax;
-    const double* thr;
-    int nq;
-    double eps;
-    double *d_ctrl, *d_draw, *d_fid, *d_tab;         // device: ctrl [Cmax][N+1], draws (host draws only), fid [Cmax][K], table [NR][Cmax]
-    int rc = RC_OK;
-    std::string err;
+struct GatherJob : ShareSpec {
+    long long Cmax;
+    double *d_ctrl, *d_draw, *d_fid, *d_tab;         // device: ctrl [Cmax][N+1], draws (NULL: the fused route), fid [Cmax][K], table [NR][Cmax]
 };
 
 int run_gather_share(GatherJob* j) {
     DeviceCtx* ctx = nullptr;
     if (int rc = get_ctx(j->device, &ctx)) return rc;
     hipStream_t st = ctx->stream;
-    const long long G = 3LL * j->N, K = j->K, Cl = j->c1 - j->c0;
+    const long long K = j->K, Cl = j->c1 - j->c0;
     RC_HIP_CHECK(hipMemsetAsync(j->d_fid, 0, (size_t)j->Cmax * K * sizeof(double), st));
-    if (Cl > 0) {
-        RC_HIP_CHECK(hipMemcpyAsync(j->d_ctrl, j->ctrl + j->c0 * (j->N + 1), (size_t)Cl * (j->N + 1) * sizeof(double),
-                                    hipMemcpyHostToDevice, st));
-        const bool fused = !j->draws && !j->ring && rc_philox_fused_pays(j->N, j->in, j->out) == 1 &&
-                           (j->kernel == RC_KERNEL_AUTO || j->kernel == RC_KERNEL_TRIDIAG_ADJ);
-        if (fused) {
-            if (int rc = rc_mc_fidelity_philox_f64_async(j->device, st, j->kernel, j->N, j->in, j->out, j->h0d, j->h0o, j->d_ctrl,
-                                                         j->seed, j->offset + (unsigned long long)(j->c0 * K * G), j->sigma, nullptr,
-                                                         Cl, K, j->d_fid))
-                return rc;
-        } else {
-            if (j->draws) {
-                RC_HIP_CHECK(hipMemcpyAsync(j->d_draw, j->draws + j->c0 * K * G, (size_t)Cl * K * G * sizeof(double),
-                                            hipMemcpyHostToDevice, st));
-            } else if (int rc = rc_draws_philox_f64_async(j->device, st, j->seed, j->offset + (unsigned long long)(j->c0 * K * G),
-                                                          Cl * K * G, j->sigma, j->d_draw)) {
-                return rc;
-            }
-            if (int rc = enqueue_fidelity(st, j->kernel, j->N, j->in, j->out, j->h0d, j->h0o, j->ring, j->d_ctrl, j->d_draw, -1, Cl, K,
-                                          j->d_fid))
-                return rc;
-        }
-    }
+    if (Cl > 0)
+        if (int rc = enqueue_share(*j, j->c0, Cl, j->d_ctrl, j->d_draw, j->d_fid, st)) return rc;
     // metric rows of all Cmax rows (the padding rows are rows of zeros: harmless, and the table keeps one shape on every device)
     double* t = j->d_tab;
     return enqueue_reduce(st, j->d_fid, j->Cmax, K, j->thr, j->nq, j->eps, t, t + 3 * j->Cmax, t + 6 * j->Cmax,
@@ -1450,45 +1451,19 @@ static int blocking_deriv(decltype(&enqueue_grad) enqueue, int per_sample, int p
                           long long draws_ctrl_stride, long long C, long long K, double* fid_out, double* second_out, double* mean_out) {
     if (int rc = device_in_range(device)) return rc;
     std::lock_guard<std::mutex> lk(g_ctx[device].mu);
-    DeviceCtx* ctx = nullptr;
-    if (int rc = get_ctx(device, &ctx)) return rc;
-    const size_t nb_ctrl = (size_t)C * (N + 1) * sizeof(double);
+    Staging ws;
+    if (int rc = get_ctx(device, &ws.ctx)) return rc;
     const size_t nb_draw = (draws_ctrl_stride == 0 ? (size_t)K * N * 3 : ((size_t)(C - 1) * draws_ctrl_stride + (size_t)K * N * 3)) *
                            sizeof(double);
-    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_second = nb_fid * per_sample, nb_mean = (size_t)C * per_row * sizeof(double);
-    const bool dc = is_device_ptr(controllers), dd = is_device_ptr(draws);
-    const bool hf = fid_out && !is_device_ptr(fid_out), hs = second_out && !is_device_ptr(second_out),
-               hm = mean_out && !is_device_ptr(mean_out);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t need = (dc ? 0 : up(nb_ctrl)) + (dd ? 0 : up(nb_draw)) + (hf ? up(nb_fid) : 0) + (hs ? up(nb_second) : 0) +
-                        (hm ? up(nb_mean) : 0);
-    if (need) {
-        if (int rc = ensure_ws(ctx, need)) return rc;
-    }
-    char* w = (char*)ctx->ws;
-    const double* d_ctrl = controllers;
-    const double* d_draw = draws;
-    double *d_fid = fid_out, *d_second = second_out, *d_mean = mean_out;
-    if (!dc) {
-        RC_HIP_CHECK(hipMemcpyAsync(w, controllers, nb_ctrl, hipMemcpyHostToDevice, ctx->stream));
-        d_ctrl = (const double*)w;
-        w += up(nb_ctrl);
-    }
-    if (!dd) {
-        RC_HIP_CHECK(hipMemcpyAsync(w, draws, nb_draw, hipMemcpyHostToDevice, ctx->stream));
-        d_draw = (const double*)w;
-        w += up(nb_draw);
-    }
-    if (hf) { d_fid = (double*)w; w += up(nb_fid); }
-    if (hs) { d_second = (double*)w; w += up(nb_second); }
-    if (hm) { d_mean = (double*)w; w += up(nb_mean); }
-    if (int rc = enqueue(ctx->stream, N, in, out, h0_diag, h0_offdiag, d_ctrl, d_draw, draws_ctrl_stride, C, K, d_fid, d_second, d_mean))
+    const size_t nb_fid = (size_t)C * K * sizeof(double);
+    const int s_ctrl = ws.in(controllers, (size_t)C * (N + 1) * sizeof(double)), s_draw = ws.in(draws, nb_draw),
+              s_fid = ws.out(fid_out, nb_fid), s_second = ws.out(second_out, nb_fid * per_sample),
+              s_mean = ws.out(mean_out, (size_t)C * per_row * sizeof(double));
+    if (int rc = ws.stage_in()) return rc;
+    if (int rc = enqueue(ws.ctx->stream, N, in, out, h0_diag, h0_offdiag, ws.ptr(s_ctrl), ws.ptr(s_draw), draws_ctrl_stride, C, K,
+                         ws.ptr(s_fid), ws.ptr(s_second), ws.ptr(s_mean)))
         return rc;
-    if (hf) RC_HIP_CHECK(hipMemcpyAsync(fid_out, d_fid, nb_fid, hipMemcpyDeviceToHost, ctx->stream));
-    if (hs) RC_HIP_CHECK(hipMemcpyAsync(second_out, d_second, nb_second, hipMemcpyDeviceToHost, ctx->stream));
-    if (hm) RC_HIP_CHECK(hipMemcpyAsync(mean_out, d_mean, nb_mean, hipMemcpyDeviceToHost, ctx->stream));
-    RC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return RC_OK;
+    return ws.stage_out();
 }
 
 extern "C" {
@@ -1815,38 +1790,16 @@ int rc_mc_fidelity_kernel_f64(int device, int kernel, int N, int in, int out, co
     if (!controllers || !draws || !fid_out) return fail(RC_EINVAL, "NULL array pointer");
     if (int rc = device_in_range(device)) return rc;
     std::lock_guard<std::mutex> lk(g_ctx[device].mu);
-    DeviceCtx* ctx = nullptr;
-    if (int rc = get_ctx(device, &ctx)) return rc;
-    const size_t nb_ctrl = (size_t)C * (N + 1) * sizeof(double);
-    const size_t nb_draw = (size_t)C * K * N * 3 * sizeof(double);
+    Staging ws;
+    if (int rc = get_ctx(device, &ws.ctx)) return rc;
     const size_t nb_fid = (size_t)C * K * sizeof(double);
-    const bool dc = is_device_ptr(controllers), dd = is_device_ptr(draws), df = is_device_ptr(fid_out);
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t need = (dc ? 0 : up(nb_ctrl)) + (dd ? 0 : up(nb_draw)) + (df ? 0 : up(nb_fid));
-    if (need) {
-        if (int rc = ensure_ws(ctx, need)) return rc;
-    }
-    char* w = (char*)ctx->ws;
-    const double* d_ctrl = controllers;
-    const double* d_draw = draws;
-    double* d_fid = fid_out;
-    if (!dc) {
-        RC_HIP_CHECK(hipMemcpyAsync(w, controllers, nb_ctrl, hipMemcpyHostToDevice, ctx->stream));
-        d_ctrl = (const double*)w;
-        w += up(nb_ctrl);
-    }
-    if (!dd) {
-        RC_HIP_CHECK(hipMemcpyAsync(w, draws, nb_draw, hipMemcpyHostToDevice, ctx->stream));
-        d_draw = (const double*)w;
-        w += up(nb_draw);
-    }
-    if (!df) d_fid = (double*)w;
-    if (int rc = enqueue_fidelity(ctx->stream, kernel, N, in, out, h0_diag, h0_offdiag, ring, d_ctrl, d_draw, -1, C, K,
-                                  d_fid))
+    const int s_ctrl = ws.in(controllers, (size_t)C * (N + 1) * sizeof(double)), s_draw = ws.in(draws, nb_fid * N * 3),
+              s_fid = ws.out(fid_out, nb_fid);
+    if (int rc = ws.stage_in()) return rc;
+    if (int rc = enqueue_fidelity(ws.ctx->stream, kernel, N, in, out, h0_diag, h0_offdiag, ring, ws.ptr(s_ctrl), ws.ptr(s_draw), -1, C,
+                                  K, ws.ptr(s_fid)))
         return rc;
-    if (!df) RC_HIP_CHECK(hipMemcpyAsync(fid_out, d_fid, nb_fid, hipMemcpyDeviceToHost, ctx->stream));
-    RC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return RC_OK;
+    return ws.stage_out();
 }
 
 int rc_reduce_f64_async(int device, void* stream, const double* fid_dev, long long C, long long K,
@@ -1875,41 +1828,17 @@ int rc_reduce_f64(int device, const double* fid, long long C, long long K, const
     if (!fid) return fail(RC_EINVAL, "NULL fid pointer");
     if (int rc = device_in_range(device)) return rc;
     std::lock_guard<std::mutex> lk(g_ctx[device].mu);
-    DeviceCtx* ctx = nullptr;
-    if (int rc = get_ctx(device, &ctx)) return rc;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t nb_fid = (size_t)C * K * sizeof(double);
-    const size_t nb_c3 = (size_t)3 * C * sizeof(double);
-    const size_t nb_q = (size_t)3 * (nq > 0 ? nq : 1) * C * sizeof(double);
-    const bool df = is_device_ptr(fid);
-    // outputs are always staged (they are small), the sorted tensor only when it is a host pointer
-    const bool ds = sorted_out && is_device_ptr(sorted_out);
-    size_t need = (df ? 0 : up(nb_fid)) + 3 * up(nb_c3) + up(nb_q) + ((sorted_out && !ds) ? up(nb_fid) : 0);
-    if (int rc = ensure_ws(ctx, need)) return rc;
-    char* w = (char*)ctx->ws;
-    const double* d_fid = fid;
-    if (!df) {
-        RC_HIP_CHECK(hipMemcpyAsync(w, fid, nb_fid, hipMemcpyHostToDevice, ctx->stream));
-        d_fid = (const double*)w;
-        w += up(nb_fid);
-    }
-    double* d_rim = (double*)w; w += up(nb_c3);
-    double* d_std = (double*)w; w += up(nb_c3);
-    double* d_min = (double*)w; w += up(nb_c3);
-    double* d_q = (double*)w;   w += up(nb_q);
-    double* d_sorted = nullptr;
-    if (sorted_out) d_sorted = ds ? sorted_out : (double*)w;
-    if (int rc = enqueue_reduce(ctx->stream, d_fid, C, K, q_thresholds, nq, dkw_eps, rim1 ? d_rim : nullptr,
-                                std_ ? d_std : nullptr, minf ? d_min : nullptr, (q && nq) ? d_q : nullptr,
-                                d_sorted, /*standalone=*/true))
+    Staging ws;
+    if (int rc = get_ctx(device, &ws.ctx)) return rc;
+    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_c3 = (size_t)3 * C * sizeof(double);
+    // the metric rows are always staged (they are small), the sorted tensor only when it is a host pointer
+    const int s_fid = ws.in(fid, nb_fid), s_rim = ws.out(rim1, nb_c3, true), s_std = ws.out(std_, nb_c3, true),
+              s_min = ws.out(minf, nb_c3, true), s_q = ws.out(nq ? q : nullptr, nb_c3 * nq, true), s_sorted = ws.out(sorted_out, nb_fid);
+    if (int rc = ws.stage_in()) return rc;
+    if (int rc = enqueue_reduce(ws.ctx->stream, ws.ptr(s_fid), C, K, q_thresholds, nq, dkw_eps, ws.ptr(s_rim), ws.ptr(s_std),
+                                ws.ptr(s_min), ws.ptr(s_q), ws.ptr(s_sorted), /*standalone=*/true))
         return rc;
-    if (rim1) RC_HIP_CHECK(hipMemcpyAsync(rim1, d_rim, nb_c3, hipMemcpyDefault, ctx->stream));
-    if (std_) RC_HIP_CHECK(hipMemcpyAsync(std_, d_std, nb_c3, hipMemcpyDefault, ctx->stream));
-    if (minf) RC_HIP_CHECK(hipMemcpyAsync(minf, d_min, nb_c3, hipMemcpyDefault, ctx->stream));
-    if (q && nq) RC_HIP_CHECK(hipMemcpyAsync(q, d_q, (size_t)3 * nq * C * sizeof(double), hipMemcpyDefault, ctx->stream));
-    if (sorted_out && !ds) RC_HIP_CHECK(hipMemcpyAsync(sorted_out, d_sorted, nb_fid, hipMemcpyDeviceToHost, ctx->stream));
-    RC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return RC_OK;
+    return ws.stage_out();
 }
 
 int rc_rim_p_f64_async(int device, void* stream, const double* fid_dev, long long C, long long K, double p,
@@ -1933,23 +1862,12 @@ int rc_rim_p_f64(int device, const double* fid, long long C, long long K, double
     if (!fid || !out) return fail(RC_EINVAL, "NULL array pointer");
     if (int rc = device_in_range(device)) return rc;
     std::lock_guard<std::mutex> lk(g_ctx[device].mu);
-    DeviceCtx* ctx = nullptr;
-    if (int rc = get_ctx(device, &ctx)) return rc;
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_out = (size_t)C * sizeof(double);
-    const bool df = is_device_ptr(fid);
-    if (int rc = ensure_ws(ctx, (df ? 0 : up(nb_fid)) + up(nb_out))) return rc;
-    char* w = (char*)ctx->ws;
-    const double* d_fid = fid;
-    if (!df) {
-        RC_HIP_CHECK(hipMemcpyAsync(w, fid, nb_fid, hipMemcpyHostToDevice, ctx->stream));
-        d_fid = (const double*)w;
-        w += up(nb_fid);
-    }
-    if (int rc = rc_rim_p_f64_async(device, ctx->stream, d_fid, C, K, p, (double*)w)) return rc;
-    RC_HIP_CHECK(hipMemcpyAsync(out, w, nb_out, hipMemcpyDefault, ctx->stream));
-    RC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return RC_OK;
+    Staging ws;
+    if (int rc = get_ctx(device, &ws.ctx)) return rc;
+    const int s_fid = ws.in(fid, (size_t)C * K * sizeof(double)), s_out = ws.out(out, (size_t)C * sizeof(double), true);
+    if (int rc = ws.stage_in()) return rc;
+    if (int rc = rc_rim_p_f64_async(device, ws.ctx->stream, ws.ptr(s_fid), C, K, p, ws.ptr(s_out))) return rc;
+    return ws.stage_out();
 }
 
 int rc_draws_philox_f64_async(int device, void* stream, unsigned long long seed, unsigned long long offset,
@@ -1973,18 +1891,12 @@ int rc_draws_philox_f64(int device, unsigned long long seed, unsigned long long 
     if (!out) return fail(RC_EINVAL, "NULL output pointer");
     if (int rc = device_in_range(device)) return rc;
     std::lock_guard<std::mutex> lk(g_ctx[device].mu);
-    DeviceCtx* ctx = nullptr;
-    if (int rc = get_ctx(device, &ctx)) return rc;
-    const bool dev_out = is_device_ptr(out);
-    double* d_out = out;
-    if (!dev_out) {
-        if (int rc = ensure_ws(ctx, (size_t)n * sizeof(double))) return rc;
-        d_out = (double*)ctx->ws;
-    }
-    if (int rc = rc_draws_philox_f64_async(device, ctx->stream, seed, offset, n, scale, d_out)) return rc;
-    if (!dev_out) RC_HIP_CHECK(hipMemcpyAsync(out, d_out, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    RC_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return RC_OK;
+    Staging ws;
+    if (int rc = get_ctx(device, &ws.ctx)) return rc;
+    const int s_out = ws.out(out, (size_t)n * sizeof(double));
+    if (int rc = ws.stage_in()) return rc;
+    if (int rc = rc_draws_philox_f64_async(device, ws.ctx->stream, seed, offset, n, scale, ws.ptr(s_out))) return rc;
+    return ws.stage_out();
 }
 
 int rc_mc_fidelity_sharded_f64(int ndev, const int* devices, int kernel, int N, int in, int out, const double* h0_diag,
@@ -2073,7 +1985,13 @@ int rc_mc_metrics_gathered_f64(rc_comm* comm, int kernel, int N, int in, int out
         bool own_tab = false, own_fid = false;
     };
     std::vector<Bufs> b(ndev);
-    std::vector<GatherJob> jobs(ndev);
+    GatherJob proto{};
+    proto.kernel = kernel; proto.N = N; proto.in = in; proto.out = out; proto.ring = ring;
+    proto.h0d = h0_diag; proto.h0o = h0_offdiag; proto.ctrl = controllers; proto.draws = draws;
+    proto.seed = philox_seed; proto.offset = philox_offset; proto.sigma = sigma;
+    proto.C = C; proto.K = K; proto.Cmax = Cmax; proto.thr = q_thresholds; proto.nq = nq; proto.eps = dkw_eps;
+    std::vector<GatherJob> jobs(ndev, proto);
+    const bool fused = philox_fused_route(draws, ring, kernel, N, in, out);     // then no draw buffer: enqueue_share goes by that
     const bool want_fid = fid_dev || fid_host;
     const long long base = C / ndev, extra = C % ndev;
     long long start = 0;
@@ -2099,15 +2017,10 @@ int rc_mc_metrics_gathered_f64(rc_comm* comm, int kernel, int N, int in, int out
         }
         hipStream_t st = ctx->stream;
         GatherJob& j = jobs[r];
-        j.device = dev; j.kernel = kernel; j.N = N; j.in = in; j.out = out; j.ring = ring;
-        j.h0d = h0_diag; j.h0o = h0_offdiag; j.ctrl = controllers; j.draws = draws;
-        j.seed = philox_seed; j.offset = philox_offset; j.sigma = sigma;
-        j.C = C; j.K = K; j.Cmax = Cmax; j.thr = q_thresholds; j.nq = nq; j.eps = dkw_eps;
+        j.device = dev;
         j.c0 = start;
         start += base + (r < extra ? 1 : 0);
         j.c1 = start;
-        const bool fused = !draws && !ring && rc_philox_fused_pays(N, in, out) == 1 &&
-                           (kernel == RC_KERNEL_AUTO || kernel == RC_KERNEL_TRIDIAG_ADJ);
         hipError_t e = hipSetDevice(dev);
         if (e == hipSuccess) e = hipMalloc((void**)&b[r].ctrl, (size_t)Cmax * (N + 1) * sizeof(double));
         if (e == hipSuccess && !fused) e = hipMalloc((void**)&b[r].draw, (size_t)Cmax * K * G * sizeof(double));

@@ -1,7 +1,10 @@
 """The blocking entries `rc_mc_fidelity_grad_f64` and `rc_mc_fidelity_sens_f64` take host or device pointers for either input and
 any output (one routine stages whatever is on the host through the device's workspace).  Every mix must give the all-host-pointer
 call's results bit for bit.  N = 3: the smallest N with two staging phases; K = 65: two tiles per row, the second with one sample,
-so that a wrong size or offset in the carving of the workspace shows."""
+so that a wrong size or offset in the carving of the workspace shows.
+
+The other blocking entries that stage through the same workspace plan - `rc_mc_fidelity_kernel_f64`, `rc_reduce_f64`,
+`rc_rim_p_f64`, `rc_draws_philox_f64` - are held to the same rule below, on the same shape."""
 import ctypes
 import importlib
 import itertools
@@ -90,3 +93,125 @@ def test_mean_only(be, inputs, reference, which):
     for ctrl_dev, draws_dev, outs_dev in ((True, False, False), (False, True, True), (True, True, True)):
         got = run(which, *inputs, K * N * 3, ctrl_dev, draws_dev, outs_dev, want=(False, False, True))
         assert np.array_equal(got[2], ref[2]), (which, ctrl_dev, draws_dev, outs_dev)
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# the other blocking entries: same shape, same sentinel, every mix against the all-host call
+# ----------------------------------------------------------------------------------------------------------------
+THR, EPS = np.array([0.9, 0.99]), 0.05                   # rc_reduce_f64: two thresholds, a DKW band
+SMALL = {"rim1": 3 * C, "std": 3 * C, "min": 3 * C, "q": 3 * len(THR) * C}      # its four small outputs, in argument order
+NDRAWS = 2 * 65 * 3 * 3 + 1                              # rc_draws_philox_f64: odd, so the last Box-Muller pair is half used
+
+
+def place(a, on_dev):
+    """an input array on the host or on the device: (owner, pointer)"""
+    import torch
+    t = torch.from_numpy(a).cuda() if on_dev else a
+    return t, ctypes.c_void_p(t.data_ptr() if on_dev else t.ctypes.data)
+
+
+def sentinel(n, where):
+    """an output of n doubles that no result equals; where: None (not requested), "host" or "dev": (owner, pointer)"""
+    import torch
+    if where is None:
+        return None, None
+    o = torch.full((n,), -7.0, dtype=torch.float64, device="cuda") if where == "dev" else np.full(n, -7.0)
+    return o, ctypes.c_void_p(o.data_ptr() if where == "dev" else o.ctypes.data)
+
+
+def call(name, *args):
+    """one blocking call on the current device; returns nothing: the outputs are the owners `sentinel` gave"""
+    import torch
+    lib = importlib.import_module("code-robchar_amd._lib").load()
+    torch.cuda.synchronize()                      # the entry runs on the library's own stream
+    rc = getattr(lib, name)(torch.cuda.current_device(), *args)
+    assert rc == 0, lib.rc_last_error()
+
+
+def host(o):
+    return None if o is None else (o if isinstance(o, np.ndarray) else o.cpu().numpy())
+
+
+def run_fidelity(ctrl, draws, ctrl_dev, draws_dev, fid_dev):
+    (kc, pc), (kd, pd) = place(ctrl, ctrl_dev), place(draws, draws_dev)
+    o, po = sentinel(C * K, "dev" if fid_dev else "host")
+    call("rc_mc_fidelity_kernel_f64", 0, N, A, B, None, None, 0, pc, pd, C, K, po)
+    return host(o)
+
+
+def run_reduce(fid, fid_dev, small, sorted_where, want=tuple(SMALL)):
+    """`small`: where the requested ones of the four small outputs live; returns {name: array} of what was requested"""
+    kf, pf = place(fid, fid_dev)
+    outs = {k: sentinel(n, small if k in want else None) for k, n in SMALL.items()}
+    outs["sorted"] = sentinel(C * K, sorted_where)
+    thr = np.ascontiguousarray(THR)
+    call("rc_reduce_f64", pf, C, K, ctypes.c_void_p(thr.ctypes.data), len(THR), EPS, *(p for _, p in outs.values()))
+    return {k: host(o) for k, (o, _) in outs.items() if o is not None}
+
+
+def run_rim_p(fid, fid_dev, out_dev):
+    kf, pf = place(fid, fid_dev)
+    o, po = sentinel(C, "dev" if out_dev else "host")
+    call("rc_rim_p_f64", pf, C, K, 2.0, po)
+    return host(o)
+
+
+def run_draws(out_dev):
+    o, po = sentinel(NDRAWS, "dev" if out_dev else "host")
+    call("rc_draws_philox_f64", 2024, 12345, NDRAWS, 0.05, po)
+    return host(o)
+
+
+def written(o):
+    return np.isfinite(o).all() and not (o == -7.0).any()
+
+
+@pytest.fixture(scope="module")
+def fid_reference(be, inputs):
+    """the all-host-pointer fidelity call; the reductions below take its result as their input"""
+    ref = run_fidelity(*inputs, False, False, False)
+    assert written(ref) and ref.min() > 0.0 and ref.max() < 1.0 + 1e-12 and np.ptp(ref) > 1e-3
+    return ref
+
+
+@pytest.fixture(scope="module")
+def reduce_reference(be, fid_reference):
+    ref = run_reduce(fid_reference, False, "host", "host")
+    assert all(written(v) for v in ref.values()) and set(ref) == set(SMALL) | {"sorted"}
+    assert np.array_equal(ref["sorted"].reshape(C, K), np.sort(fid_reference.reshape(C, K), axis=1))
+    assert np.abs(ref["rim1"][:C] - (1.0 - fid_reference.reshape(C, K)).mean(axis=1)).max() < 1e-12
+    return ref
+
+
+def test_fidelity_every_mix(be, inputs, fid_reference):
+    for mix in itertools.product((False, True), repeat=3):
+        assert np.array_equal(run_fidelity(*inputs, *mix), fid_reference), mix
+
+
+def test_reduce_every_mix(be, fid_reference, reduce_reference):
+    for fid_dev, sorted_where, small in itertools.product((False, True), (None, "host", "dev"), ("host", "dev")):
+        got = run_reduce(fid_reference, fid_dev, small, sorted_where)
+        assert set(got) == set(SMALL) | ({"sorted"} if sorted_where else set())
+        for k, g in got.items():
+            assert np.array_equal(g, reduce_reference[k]), (k, fid_dev, sorted_where, small)
+
+
+@pytest.mark.parametrize("only", list(SMALL))
+def test_reduce_one_small_output_alone(be, fid_reference, reduce_reference, only):
+    """one of the four small outputs requested: the others take no workspace and the kernel gets NULL for them"""
+    for small in ("host", "dev"):
+        got = run_reduce(fid_reference, True, small, None, want=(only,))
+        assert list(got) == [only] and np.array_equal(got[only], reduce_reference[only]), (only, small)
+
+
+def test_rim_p_every_mix(be, fid_reference):
+    ref = run_rim_p(fid_reference, False, False)
+    assert written(ref) and (ref > 0.0).all() and ref[0] != ref[1]
+    for mix in itertools.product((False, True), repeat=2):
+        assert np.array_equal(run_rim_p(fid_reference, *mix), ref), mix
+
+
+def test_draws_philox_host_and_device(be):
+    ref = run_draws(False)
+    assert written(ref) and 0.03 < ref.std() < 0.07 and len(np.unique(ref)) == NDRAWS
+    assert np.array_equal(run_draws(True), ref)
