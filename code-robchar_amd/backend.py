@@ -507,14 +507,16 @@ def mc_fidelity_sens_philox(controllers, n_draws: int, nspin: int, inspin: int, 
     `sigma`: a float, or a (C,) tensor / array (one scale per controller row: every sigma level of an algorithm in one launch).
     The mean rho in "mean"[:, 1] is taken over the generated draws sigma z: d fav / d ln(sigma) at the row's sigma; a
     row with sigma = 0 gives the nominal sensitivity with rho = 0.  Chain topology, N <= `max_nspin_grad()`."""
-    return _fidelity_derivatives_philox("sens", SENS_OUTPUTS, lambda C, K, N: {"fid": (C, K), "sens": (C, K, N, 3), "mean": (C, 3 * N + 2)},
+    return _fidelity_derivatives_philox("sens_philox", SENS_OUTPUTS, lambda C, K, N: {"fid": (C, K), "sens": (C, K, N, 3), "mean": (C, 3 * N + 2)},
                                         controllers, n_draws, nspin, inspin, outspin, seed, offset, sigma, h0_diag, h0_offdiag, want, ())
 
 
 def _fidelity_derivatives_philox(which, outputs, shapes_of, controllers, n_draws, nspin, inspin, outspin, seed, offset, sigma,
-                                 h0_diag, h0_offdiag, want, extra_args):
-    """`mc_fidelity_sens_philox` (which = "sens") and `mc_fidelity_grad_philox` ("grad"): the two C entries differ in their outputs
-    and in `extra_args`, which the entry takes between `sigma_rows` and `C`.  Everything is validated before the library is loaded."""
+                                 h0_diag, h0_offdiag, want, extra_args, late_args=None):
+    """`mc_fidelity_sens_philox` (which = "sens_philox"), `mc_fidelity_grad_philox` ("grad_philox") and `mc_fidelity_grad_listed`
+    ("grad_listed"): the C entries differ in their outputs, in `extra_args`, which the entry takes between `sigma_rows` and `C`,
+    and in `late_args(device)` -> what it takes between `K` and the outputs (tensors are brought to the controllers' device
+    there).  Everything is validated before the library is loaded."""
     import torch
     _check_geometry(nspin, inspin, outspin)
     want = tuple(want)
@@ -548,10 +550,12 @@ def _fidelity_derivatives_philox(which, outputs, shapes_of, controllers, n_draws
     res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
     ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in outputs]
     stream = torch.cuda.current_stream(dev).cuda_stream
-    entry = getattr(lib, f"rc_mc_fidelity_{which}_philox_f64_async")
+    entry = getattr(lib, f"rc_mc_fidelity_{which}_f64_async")
+    late, keep = late_args(dev) if late_args is not None else ((), None)     # (`keep`: the tensors behind the pointers in `late`)
     _lib.check(entry(dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o),
                      ctypes.c_void_p(ctrl.data_ptr()), int(seed) & (2 ** 64 - 1), int(offset), 0.0 if rows is not None else float(sigma),
-                     ctypes.c_void_p(rows.data_ptr()) if rows is not None else None, *extra_args, C, K, *ptr))
+                     ctypes.c_void_p(rows.data_ptr()) if rows is not None else None, *extra_args, C, K, *late, *ptr))
+    del keep
     return res
 
 
@@ -574,10 +578,67 @@ def mc_fidelity_grad_philox(controllers, n_draws: int, nspin: int, inspin: int, 
     `philox_normal((1, K, N, 3), ...)`, bit for bit.  Neither tensor is ever built.
     `sigma`: a float, or a (C,) tensor / array (one scale per controller row); a row with sigma = 0 gives K identical samples.
     Chain topology, N <= `max_nspin_grad()`.  No automatic routing: DESIGN.md has the timing against the two-kernel route."""
-    return _fidelity_derivatives_philox("grad", GRAD_PHILOX_OUTPUTS,
+    return _fidelity_derivatives_philox("grad_philox", GRAD_PHILOX_OUTPUTS,
                                         lambda C, K, N: {"fid": (C, K), "grad": (C, K, N + 1), "mean": (C, N + 2), "moment": (C, N + 2)},
                                         controllers, n_draws, nspin, inspin, outspin, seed, offset, sigma, h0_diag, h0_offdiag, want,
                                         (int(bool(shared)),))
+
+
+GRAD_LISTED_OUTPUTS = ("fid", "grad", "sum")
+
+
+def mc_fidelity_grad_listed(controllers, n_draws: int, listed, weights=None, *, nspin: int, inspin: int, outspin: int, seed: int,
+                            offset: int = 0, sigma=0.05, shared: bool = False, h0_diag=None, h0_offdiag=None,
+                            want=GRAD_LISTED_OUTPUTS):
+    """`mc_fidelity_grad_philox` over a chosen LIST of each row's `n_draws` draws, with weights on the row sums
+    (`rc_mc_fidelity_grad_listed_f64_async`): only the listed samples are computed.  controllers (C, N+1) torch CUDA tensor (a NumPy
+    array is uploaded); `listed` (C, L) int32 CUDA tensor (an integer NumPy array is uploaded): slot s of row c is draw
+    k = listed[c, s] of that row - the stream element offset + ((c K + k) N + i) 3 + s', with shared=True offset + (k N + i) 3 + s' -,
+    a value outside 0 .. K - 1 an EMPTY slot, repeats allowed; `weights` (C, L) float64 or None (= 1).  -> dict of torch tensors on
+    the controllers' device, the entries named in `want`, enqueued on the current stream:
+
+        "fid" (C, L), "grad" (C, L, N+1)      per slot, NaN in an empty slot,
+        "sum" (C, N+2) = sum_s weights[c, s] (F, dF/dx)(c, listed[c, s])             fixed order, no atomics: same inputs, same bits.
+
+    A sample's bits depend on (c, k) and the other arguments only - not on L, the slot or what else is listed.  Against
+    `mc_fidelity_grad_philox` on all K draws they agree to rounding, not bit for bit (there the wave votes the QL sweep counts).
+    `noise.tail_weights` makes the list and weights of CVaR_alpha.  `sigma`, NaN rows, chain topology, N <= `max_nspin_grad()`: as
+    `mc_fidelity_grad_philox`."""
+    if _is_torch(listed):
+        import torch
+        if listed.dtype != torch.int32:
+            raise ValueError("listed: an int32 tensor")
+    else:
+        listed = np.asarray(listed)
+        if listed.dtype.kind not in "iu":
+            raise ValueError("listed: an integer array")
+        listed = np.ascontiguousarray(listed, dtype=np.int32)
+    nrows = int(controllers.shape[0]) if hasattr(controllers, "shape") else len(controllers)
+    if listed.ndim != 2 or int(listed.shape[0]) != nrows:
+        raise ValueError(f"listed: expected ({nrows}, L), got {tuple(listed.shape)}")
+    L = int(listed.shape[1])
+    if weights is not None:
+        if not _is_torch(weights):
+            weights = np.ascontiguousarray(weights, dtype=np.float64)
+        elif str(weights.dtype) != "torch.float64":
+            raise ValueError("weights: a float64 tensor")
+        if tuple(weights.shape) != (nrows, L):
+            raise ValueError(f"weights: expected {(nrows, L)}, got {tuple(weights.shape)}")
+
+    def late_args(dev):
+        import torch
+        lst = (listed if _is_torch(listed) else torch.from_numpy(listed)).to(device=dev).contiguous()
+        wts = None if weights is None else (weights if _is_torch(weights) else torch.from_numpy(weights)).to(device=dev).contiguous()
+        return ((ctypes.c_void_p(lst.data_ptr()), ctypes.c_void_p(wts.data_ptr()) if wts is not None else None, L), (lst, wts))
+
+    res = _fidelity_derivatives_philox("grad_listed", GRAD_LISTED_OUTPUTS,
+                                       lambda C, K, N: {"fid": (C, L), "grad": (C, L, N + 1), "sum": (C, N + 2)},
+                                       controllers, n_draws, nspin, inspin, outspin, seed, offset, sigma, h0_diag, h0_offdiag, want,
+                                       (int(bool(shared)),), late_args)
+    if int(n_draws) == 0 or L == 0:                  # (the entry writes nothing then: every slot is empty)
+        for k, v in res.items():
+            v.fill_(0.0 if k == "sum" else float("nan"))
+    return res
 
 
 def mc_fidelity_directional(controllers, idx, ab, nspin: int, inspin: int, outspin: int, n_draws: int, h0_diag=None,

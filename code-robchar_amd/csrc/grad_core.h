@@ -120,8 +120,9 @@ RC_HD void grad_load_matrix(const double* x, const double* h0d, const double* h0
 }
 
 // Fast path, one pass: eigenvalues in s.d, V[site[q]][k] in s.z[q][k] (a row with site < 0 is zero).  Returns false - per
-// lane - on the sweep cap.
-template <int N, int R>
+// lane - on the sweep cap.  FREEZE: tridiag_ql2_fast's - every lane performs exactly the sweeps it would perform alone, so its
+// result does not depend on which other samples share its wave (mc_fid_grad_listed_kernel, whose waves are packed from a list).
+template <int N, int R, bool FREEZE = false>
 RC_HD bool grad_eigensystem_fast(const double (&d)[N], const double (&e)[N], const int (&site)[R], TriEig<N, R>& s) {
     // (the unit rows are wave-uniform: left alone the compiler keeps all R N of them in SCALAR registers until the first rotation
     // touches them and spills ~200 of those; two opaque per-lane constants put them where they end up anyway)
@@ -137,10 +138,10 @@ RC_HD bool grad_eigensystem_fast(const double (&d)[N], const double (&e)[N], con
         for (int q = 0; q < R; ++q) s.z[q][i] = (site[q] == i) ? one : zero;
     }
 #if RC_GRAD_FORCE_GENERAL
-    (void)tridiag_ql2_fast<N, R>(s);
+    (void)tridiag_ql2_fast<N, R, FREEZE>(s);
     return false;
 #else
-    return tridiag_ql2_fast<N, R>(s);
+    return tridiag_ql2_fast<N, R, FREEZE>(s);
 #endif
 }
 

@@ -103,4 +103,27 @@ struct GradPhiloxParams {
     StaticH h0;
 };
 
+// GradPhiloxParams over a list of each row's draws (k_fidelity_grad_listed.inc.h): slot s of row c is sample (c, list[c][s]) of
+// the same stream convention - a value outside 0 .. K - 1 is an empty slot -; the tiles cover the L slots of a row, the outputs
+// are per slot and the part rows carry the sums weighted by weight[c][s].
+struct GradListedParams {
+    const double* ctrl;    // [C][N+1]
+    double* fid;           // [C][L] or NULL
+    double* grad;          // [C][L][N+1] or NULL
+    double* part;          // [ntiles][N+2] per-tile weighted sums for the row sums, or NULL
+    long long C, K;
+    long long tiles_per_ctrl;         // ceil(L / 64)
+    long long ntiles;                 // C * tiles_per_ctrl
+    int in, out;
+    int shared;                       // 1: one draw set for every controller row
+    unsigned long long seed;
+    unsigned long long offset;        // stream element of sample (c = 0, k = 0), site 0, slot 0
+    const double* sigma_rows;         // [C] scale per controller row, or NULL: `sigma` for all
+    double sigma;
+    const int* list;       // [C][L]
+    const double* weight;  // [C][L], or NULL: 1 for every slot
+    long long L;
+    StaticH h0;
+};
+
 }  // namespace rckp

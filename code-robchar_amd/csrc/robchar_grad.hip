@@ -17,13 +17,14 @@ namespace {
 
 using rckp::GradParams;
 using rckp::GradPhiloxParams;
+using rckp::GradListedParams;
 using rckp::SensParams;
 using rckp::SensPhiloxParams;
 typedef __attribute__((address_space(1))) const void* rc_gptr_t;
 typedef __attribute__((address_space(3))) void* rc_lptr_t;
 
 // tiles in which some sample's QL hit the sweep cap and took the textbook routine (diagnostic; rare path only); counted by
-// mc_fid_grad_kernel and mc_fid_grad_philox_kernel
+// mc_fid_grad_kernel, mc_fid_grad_philox_kernel and mc_fid_grad_listed_kernel
 __device__ unsigned long long g_grad_general_tiles = 0;
 
 // the same for mc_fid_sens_kernel and mc_fid_sens_philox_kernel
@@ -34,6 +35,7 @@ __device__ unsigned long long g_sens_general_tiles = 0;
 #include "philox_core.inc.h"
 #include "k_fidelity_sens_philox.inc.h"
 #include "k_fidelity_grad_philox.inc.h"
+#include "k_fidelity_grad_listed.inc.h"
 
 }  // namespace
 
@@ -55,6 +57,7 @@ RC_LAUNCH_2_TO_12(launch_grad, mc_fid_grad_kernel, rckp::GradParams)
 RC_LAUNCH_2_TO_12(launch_sens, mc_fid_sens_kernel, rckp::SensParams)
 RC_LAUNCH_2_TO_12(launch_sens_philox, mc_fid_sens_philox_kernel, rckp::SensPhiloxParams)
 RC_LAUNCH_2_TO_12(launch_grad_philox, mc_fid_grad_philox_kernel, rckp::GradPhiloxParams)
+RC_LAUNCH_2_TO_12(launch_grad_listed, mc_fid_grad_listed_kernel, rckp::GradListedParams)
 #undef RC_LAUNCH_2_TO_12
 #undef RC_LAUNCH_CASE
 
@@ -92,6 +95,13 @@ __attribute__((visibility("hidden"))) int rc_grad_philox_launch(int N, void* s, 
                                                                 double* moment) {
     return launch_row_means(launch_grad_philox(N, (hipStream_t)s, *p), (hipStream_t)s, p->part, mean, moment, p->moments != 0,
                             N + 2, p->tiles_per_ctrl, p->K, p->C);
+}
+
+// (the part rows carry the WEIGHTED sums over the listed slots; `sum` [C][N+2] is their row sum: the second pass with K = 1, whose
+// division by 1.0 is exact)
+__attribute__((visibility("hidden"))) int rc_grad_listed_launch(int N, void* s, const rckp::GradListedParams* p, double* sum) {
+    return launch_row_means(launch_grad_listed(N, (hipStream_t)s, *p), (hipStream_t)s, p->part, sum, nullptr, false, N + 2,
+                            p->tiles_per_ctrl, 1, p->C);
 }
 
 // device address of g_grad_general_tiles

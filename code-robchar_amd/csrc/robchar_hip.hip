@@ -63,6 +63,7 @@ __attribute__((visibility("hidden"))) int rc_large_counter_addr(int which, void*
 __attribute__((visibility("hidden"))) int rc_grad_launch(int N, void* stream, const rckp::GradParams* p, double* mean);
 __attribute__((visibility("hidden"))) int rc_grad_philox_launch(int N, void* stream, const rckp::GradPhiloxParams* p, double* mean,
                                                                 double* moment);
+__attribute__((visibility("hidden"))) int rc_grad_listed_launch(int N, void* stream, const rckp::GradListedParams* p, double* sum);
 __attribute__((visibility("hidden"))) int rc_grad_counter_addr(void** addr);
 __attribute__((visibility("hidden"))) int rc_sens_launch(int N, void* stream, const rckp::SensParams* p, double* mean);
 __attribute__((visibility("hidden"))) int rc_sens_counter_addr(void** addr);
@@ -1362,7 +1363,7 @@ static long long read_tile_counter(int device, int reset, const Sym& symbol, int
 // ------------------------------------------------------------------------------------------------
 // the derivative family (robchar_grad.hip): what its entries share on the host
 // ------------------------------------------------------------------------------------------------
-// Argument checks of the five entries of the derivative family - all before any HIP call.  `what`: the kernel's name in the
+// Argument checks of the entries of the derivative family - all before any HIP call.  `what`: the kernel's name in the
 // N > RC_MAX_NSPIN_GRAD refusal; `outs`: the output arguments, of which `any_out` says whether one is set.  `stride` set: the
 // entry takes a draw tensor (its default is filled in); NULL: it generates its draws from `sigma` / `sigma_rows`.
 // *empty: nothing to do (RC_OK).
@@ -1696,6 +1697,38 @@ int rc_mc_fidelity_grad_philox_f64_async(int device, void* stream, int N, int in
     p.sigma = sigma;
     return launch_with_part(s, p, mean_out_dev || moment_out_dev, (N + 2) * (p.moments ? 2 : 1), "rc_grad_philox_launch",
                             [&] { return rc_grad_philox_launch(N, (void*)s, &p, mean_out_dev, moment_out_dev); });
+}
+
+int rc_mc_fidelity_grad_listed_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,
+                                         const double* h0_offdiag, const double* controllers_dev, unsigned long long seed,
+                                         unsigned long long offset, double sigma, const double* sigma_rows_dev, int shared_draws,
+                                         long long C, long long K, const int* list_dev, const double* weight_dev, long long L,
+                                         double* fid_out_dev, double* grad_out_dev, double* sum_out_dev) {
+    bool empty = false;
+    if (int rc = check_deriv_args("fidelity-gradient", "fid_out, grad_out and sum_out", N, in, out, controllers_dev, nullptr, nullptr,
+                                  sigma, sigma_rows_dev, C, K, fid_out_dev || grad_out_dev || sum_out_dev, &empty))
+        return rc;
+    if (L < 0) return fail(RC_EINVAL, "L must be non-negative");
+    if (empty || L == 0) return RC_OK;
+    if (!list_dev) return fail(RC_EINVAL, "NULL array pointer (list)");
+    if ((C * ((L + 63) / 64)) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    RC_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    rckp::GradListedParams p{};
+    fill_deriv_params(p, N, in, out, h0_diag, h0_offdiag, controllers_dev, C, K, fid_out_dev);
+    p.tiles_per_ctrl = (L + 63) / 64;              // the tiles cover the L slots of a row, not its K draws
+    p.ntiles = C * p.tiles_per_ctrl;
+    p.grad = grad_out_dev;
+    p.shared = shared_draws ? 1 : 0;
+    p.seed = seed;
+    p.offset = offset;
+    p.sigma_rows = sigma_rows_dev;
+    p.sigma = sigma;
+    p.list = list_dev;
+    p.weight = weight_dev;
+    p.L = L;
+    return launch_with_part(s, p, sum_out_dev != nullptr, N + 2, "rc_grad_listed_launch",
+                            [&] { return rc_grad_listed_launch(N, (void*)s, &p, sum_out_dev); });
 }
 
 int rc_mc_fidelity_philox_f64_async(int device, void* stream, int kernel, int N, int in, int out, const double* h0_diag,

@@ -78,6 +78,50 @@ def moments_from_sums(mean, moment):
     return {"fav": fav, "grad_fav": grad_fav, "var": var, "grad_var": grad_var, "std": std, "grad_std": grad_std}
 
 
+def tail_weights(fid, alpha: float):
+    """List and weights of the lower tail of each row of `fid` (C, K) for `backend.mc_fidelity_grad_listed`: with them its "sum"
+    row is (CVaR_alpha F, d CVaR_alpha / dx) of the row's empirical distribution (Rockafellar - Uryasev; the gradient holds
+    almost everywhere: where the tail set does not change).  NumPy array or torch tensor in, the same kind out:
+
+        listed   (C, m) int32     m = ceil(alpha K): the indices of the m smallest values of the row, SORTED ASCENDING (one canonical
+                                  summation order); ties go to the lower index
+        weights  (C, m) float64   1 / (alpha K), and (alpha K - (m - 1)) / (alpha K) on the m-th smallest: the exact CVaR of the
+                                  empirical distribution; every row sums to 1
+
+    alpha in (0, 1]: alpha = 1 gives every index with weight 1 / K (the mean), alpha K < 1 the minimum with weight 1.  A row
+    with a NaN in it gives empty slots (-1) with weight 0."""
+    alpha = float(alpha)
+    if not (0.0 < alpha <= 1.0):
+        raise ValueError("alpha must be in (0, 1]")
+    if fid.ndim != 2:
+        raise ValueError("fid: expected (C, K)")
+    K = int(fid.shape[1])
+    if K == 0:
+        raise ValueError("fid: K must be positive")
+    ak = alpha * K
+    m = min(K, int(np.ceil(ak)))
+    w_body, w_last = 1.0 / ak, (ak - (m - 1)) / ak
+    if backend._is_torch(fid):
+        import torch
+        order = torch.argsort(fid, dim=1, stable=True)[:, :m]
+        last = order[:, m - 1:m]
+        listed = torch.sort(order, dim=1).values
+        weights = torch.full(listed.shape, w_body, dtype=torch.float64, device=fid.device)
+        weights[listed == last] = w_last
+        bad = torch.isnan(fid).any(dim=1, keepdim=True).expand_as(listed)
+        listed = listed.to(torch.int32)
+        listed[bad] = -1
+        weights[bad] = 0.0
+        return listed, weights
+    fid = np.asarray(fid, dtype=np.float64)
+    order = np.argsort(fid, axis=1, kind="stable")[:, :m]
+    last = order[:, m - 1:m]
+    listed = np.sort(order, axis=1)
+    weights = np.where(listed == last, w_last, w_body)
+    bad = np.isnan(fid).any(axis=1, keepdims=True)
+    return np.where(bad, -1, listed).astype(np.int32), np.where(bad, 0.0, weights)
+
+
 class noise_model_base:
     """Same constructor, attributes and methods as the reference class (noise_model.py:50-115)."""
 
@@ -320,6 +364,58 @@ class noise_model_base:
                                               sigma=sigma, shared=shared, h0_diag=diag, h0_offdiag=off, want=("mean", "moment"))
         mean, moment = (v.cpu().numpy() if backend._is_torch(v) else np.asarray(v) for v in (res["mean"], res["moment"]))
         return {k: v.copy() for k, v in moments_from_sums(mean, moment).items()}
+
+    def fidelity_cvar_philox(self, controllers, n_draws: int, seed: int, alpha: float, sigma=None, offset: int = 0,
+                             shared: bool = False):
+        """CVaR_alpha of the fidelity - the mean of the worst alpha K of `n_draws` counter-based draws per controller - with its
+        gradient with respect to the controller: {"cvar" (C,), "grad_cvar" (C, N+1), "var" (C,)}, NumPy arrays.  Three launches,
+        nothing per sample leaves the device: the fidelities of all K draws (`backend.mc_fidelity_philox`, the mixed-precision
+        kernel), `tail_weights` on the device, and ONE `backend.mc_fidelity_grad_listed` launch over the selected ceil(alpha K)
+        draws with want=("sum",).  "cvar" is that launch's own weighted sum, so value and gradient come from one evaluation;
+        "var" - the value at risk - is the largest selected fidelity.  The gradient is that of the empirical CVaR where the tail
+        set is locally constant (almost everywhere).  A NaN row gives NaN.  alpha = 1: the mean and its gradient.
+        `sigma`, `offset`, `shared` and the restrictions (chain topology, real static couplings): as `fidelity_moments_philox`."""
+        diag, off, ring, imag = self._static_terms()
+        if ring:
+            raise NotImplementedError("the fidelity gradient is implemented for the chain topology only")
+        if imag.any():
+            raise NotImplementedError("draws generated inside the gradient kernel: real static couplings only (complex ones: "
+                                      "fidelity_grad_from_draws on a draw tensor)")
+        if not (0.0 < float(alpha) <= 1.0):
+            raise ValueError("alpha must be in (0, 1]")
+        if int(n_draws) < 1:
+            raise ValueError("n_draws must be positive")
+        if sigma is None:
+            sigma = float(self.rng.args.get("scale", self.noise))
+        if not backend._is_torch(controllers):
+            controllers = np.asarray(controllers, dtype=np.float64).reshape(-1, self.Nspin + 1)
+        import torch
+        N, K = self.Nspin, int(n_draws)
+        ctrl = (controllers if backend._is_torch(controllers) else torch.from_numpy(controllers).to(backend.compute_device()))
+        ctrl = ctrl.to(dtype=torch.float64).contiguous()
+        rows = np.ndim(sigma) > 0
+        if rows:
+            sigma = (sigma if backend._is_torch(sigma) else torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)))
+            sigma = sigma.to(device=ctrl.device, dtype=torch.float64)
+        if not shared:
+            fid = backend.mc_fidelity_philox(ctrl, K, N, self.inspin, self.outspin, seed, offset=offset, sigma=sigma, h0_diag=diag,
+                                             h0_offdiag=off)
+        elif not rows:
+            with torch.cuda.device(ctrl.device):
+                draws = backend.philox_normal((1, K, N, 3), seed, scale=float(sigma), offset=offset, as_torch=True)
+            fid = backend.mc_fidelity(ctrl, draws, N, self.inspin, self.outspin, h0_diag=diag, h0_offdiag=off)
+        else:                                      # (one draw set, one scale per row: no fidelity-only kernel takes that)
+            fid = backend.mc_fidelity_grad_philox(ctrl, K, N, self.inspin, self.outspin, seed, offset=offset, sigma=sigma, shared=True,
+                                                  h0_diag=diag, h0_offdiag=off, want=("fid",))["fid"]
+        listed, weights = tail_weights(fid, alpha)
+        res = backend.mc_fidelity_grad_listed(ctrl, K, listed, weights, nspin=N, inspin=self.inspin, outspin=self.outspin, seed=seed,
+                                              offset=offset, sigma=sigma, shared=shared, h0_diag=diag, h0_offdiag=off, want=("sum",))
+        var = torch.gather(fid, 1, listed.clamp(min=0).long()).max(dim=1).values       # (a NaN row gathers NaN)
+        total = res["sum"].cpu().numpy()
+        nan = np.isnan(ctrl.cpu().numpy()).any(axis=1)
+        var = var.cpu().numpy().copy()
+        var[nan] = np.nan
+        return {"cvar": total[:, 0].copy(), "grad_cvar": total[:, 1:].copy(), "var": var}
 
     def nominal_sensitivity(self, controllers):
         """(C, N, 3): dF/d(perturbation) of the unperturbed system per structured direction - the differential sensitivity at

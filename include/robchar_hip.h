@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 10      /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 11      /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -61,7 +61,8 @@ extern "C" {
                                   8: + rc_mc_fidelity_sens_f64_async, rc_mc_fidelity_sens_f64, rc_stats_sens_general_tiles
                                      (additive);
                                   9: + rc_mc_fidelity_sens_philox_f64_async (additive);
-                                  10: + rc_mc_fidelity_grad_philox_f64_async (additive) */
+                                  10: + rc_mc_fidelity_grad_philox_f64_async (additive);
+                                  11: + rc_mc_fidelity_grad_listed_f64_async (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -281,6 +282,35 @@ int rc_mc_fidelity_grad_philox_f64_async(int device, void* stream, int N, int in
                                          unsigned long long seed, unsigned long long offset, double sigma,
                                          const double* sigma_rows_dev, int shared_draws, long long C, long long K,
                                          double* fid_out_dev, double* grad_out_dev, double* mean_out_dev, double* moment_out_dev);
+
+/* (ABI 11) rc_mc_fidelity_grad_philox_f64_async over a caller-chosen LIST of each row's K draws, with caller-chosen weights on
+ * the row sums:   sum_out[c] = sum_s  w[c][s] * (F, dF/dx_0 .. dF/dx_N)(c, list[c][s]),   s = 0 .. L - 1.
+ * Tail weights on the worst alpha K draws give CVaR_alpha and its gradient (noise.tail_weights), softmax weights the entropic
+ * risk, a smoothed step's derivative a yield; repeated indices (bootstrap resamples) are allowed.  Only the listed samples are
+ * computed.  Slot s of row c is sample (c, k = list_dev[c][s]) of the stream conventions above (`shared_draws`, `offset`, `sigma` /
+ * sigma_rows_dev[c]): offset + ((c K + k) N + i) 3 + s', shared draws offset + (k N + i) 3 + s'.  A value outside 0 .. K - 1 is an
+ * EMPTY slot: NaN in fid_out / grad_out, nothing added to sum_out.
+ * Outputs, each optional (all three NULL: RC_EINVAL "no output"):
+ *     fid_out [C][L], grad_out [C][L][N+1]   per slot;
+ *     sum_out [C][N+2]   the weighted sums above; weight_dev [C][L], or NULL: w = 1 (no multiplication).  Every product is rounded
+ *                        once, the slots are added in a fixed order, no atomics: same inputs, same bits.  A row of only empty
+ *                        slots gives 0.
+ * A NaN controller row gives NaN in all three outputs.  A sample's fid and grad bits depend on (c, k) and the other arguments
+ * only - not on L, not on the slot, not on what else is listed (every lane runs exactly the QL sweeps it would run alone).
+ * Against rc_mc_fidelity_grad_philox_f64_async on all K draws a listed sample therefore AGREES TO ROUNDING, NOT BIT FOR BIT - not
+ * even with list = 0 .. K - 1: there the whole wave votes the sweep count for each eigenvalue index, so a sample's last bits depend
+ * on its 63 wave-mates, and a listed sample sits among other mates.  Tested bound on fid: 64 N eps max(1, T ||H||).
+ * Argument checks before any HIP call, in the family's order and with its codes and texts; then L < 0: RC_EINVAL; C, K or L = 0:
+ * RC_OK, nothing written; list_dev NULL: RC_EINVAL.  N = 2 .. RC_MAX_NSPIN_GRAD (RC_ENOSUP above: "N <= 12"), chain topology.
+ * The sweep-cap fallback counts into rc_stats_grad_general_tiles.  sum_out's scratch is allocated and freed in stream order
+ * (hipMallocAsync), as for mean_out above, and the same stream-capture rules hold.  Enqueue-only: device pointers, launched on
+ * `stream`.  Timing: DESIGN.md ("Listed-sample gradient"); no automatic routing anywhere. */
+int rc_mc_fidelity_grad_listed_f64_async(int device, void* stream, int N, int in, int out,
+                                         const double* h0_diag, const double* h0_offdiag, const double* controllers_dev,
+                                         unsigned long long seed, unsigned long long offset, double sigma,
+                                         const double* sigma_rows_dev, int shared_draws, long long C, long long K,
+                                         const int* list_dev, const double* weight_dev, long long L,
+                                         double* fid_out_dev, double* grad_out_dev, double* sum_out_dev);
 
 /* (ABI 6) 1 when the kernel above is the faster of the two bit-identical routes for this geometry (N <= 13, or N = 14 with
  * {in, out} = {0, N-1}), else 0; 0 everywhere when ROBCHAR_PHILOX_FUSED=0 is in the environment (read per call).  The ONE

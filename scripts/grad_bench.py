@@ -12,7 +12,13 @@ Cache, N = 5, 7, 10 at 100 x 10 000 on the delocalised controller sets; per-samp
 delocalised sets: (a) `philox_normal` + `mc_fidelity_grad`, mean only; (b) the fused kernel, mean only; (c) the fused kernel,
 mean + moment.  The routes alternate in one process, `--launches` launches after `--warmup`, HIP events, `--repeats` repeats.
 
-    python scripts/grad_bench.py --philox [--out profiles/grad_philox_bench.txt]"""
+    python scripts/grad_bench.py --philox [--out profiles/grad_philox_bench.txt]
+
+--listed runs the CVaR leg: (a) the full launch, `mc_fidelity_grad_philox` mean only, against (b) the fidelity launch over all K
+draws (`mc_fidelity_philox`) + the selection on the device (`noise.tail_weights`) + the listed launch over the selected alpha K
+(`mc_fidelity_grad_listed`, sum only), alpha = 0.1 and 0.01, N = 5, 7, 10, 12 at 100 x 10 000, sigma = 0.05, same alternation.
+
+    python scripts/grad_bench.py --listed [--out profiles/grad_listed_bench.txt]"""
 import argparse
 import importlib
 import os
@@ -77,12 +83,63 @@ def philox_leg(args, be, dev, C, K):
     return "\n".join(lines) + "\n"
 
 
+def listed_leg(args, be, dev, C, K):
+    import torch
+    import chain_checks as cc
+    from conftest import highfid_workload
+    noise = importlib.import_module("code-robchar_amd.noise")
+    sigma, seed, alphas = 0.05, 7, (0.1, 0.01)
+    lines = [f"# CVaR route (mc_fidelity_philox + tail_weights + mc_fidelity_grad_listed, sum only) against the full launch "
+             f"(mc_fidelity_grad_philox, mean only), {C} x {K}, sigma = {sigma}, {args.launches} launches after {args.warmup}, routes "
+             f"alternated, {args.repeats} repeats (min .. max, us per evaluation), HIP events",
+             f"# device: {torch.cuda.get_device_name(dev)}",
+             "# N  in out | (a) full launch us | " + " | ".join(f"(b) alpha = {al} us | (b)/(a)" for al in alphas) + " (of the minima)"]
+    work = {w[0]: w for w in (highfid_workload(cid, C=C) for cid in (2, 3, 5))}
+    work[12] = (12, 0, 11, cc.deloc_ctrl(np.random.default_rng(12), C, 12, 0.5), None)
+
+    def timed_calls(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.launches):
+            fn()
+        e1.record()
+        torch.cuda.synchronize(dev)
+        return e0.elapsed_time(e1) * 1e3 / args.launches
+
+    def spread(v):
+        return f"{min(v):9.1f} .. {max(v):9.1f}"
+
+    for N in (5, 7, 10, 12):
+        _, a, b, ctrl, h0 = work[N]
+        ct = torch.from_numpy(ctrl).to(dev)
+        fid = torch.empty((C, K), dtype=torch.float64, device=dev)
+
+        def tail(alpha):
+            be.mc_fidelity_philox(ct, K, N, a, b, seed, sigma=sigma, h0_diag=h0, out=fid)
+            listed, weights = noise.tail_weights(fid, alpha)
+            be.mc_fidelity_grad_listed(ct, K, listed, weights, nspin=N, inspin=a, outspin=b, seed=seed, sigma=sigma, h0_diag=h0,
+                                       want=("sum",))
+
+        ta, tb = [], {al: [] for al in alphas}
+        for _ in range(args.repeats):
+            ta.append(timed_calls(lambda: be.mc_fidelity_grad_philox(ct, K, N, a, b, seed, sigma=sigma, h0_diag=h0, want=("mean",))))
+            for al in alphas:
+                tb[al].append(timed_calls(lambda: tail(al)))
+        lines.append(f"{N:3d} {a:3d} {b:3d} | {spread(ta)} | " + " | ".join(f"{spread(tb[al])} | {min(tb[al]) / min(ta):5.2f}" for al in alphas))
+        print(lines[-1], flush=True)
+    return "\n".join(lines) + "\n"
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--launches", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--out", default=None)
     ap.add_argument("--philox", action="store_true", help="the fused-against-two-kernel leg instead of the kernel table")
+    ap.add_argument("--listed", action="store_true", help="the CVaR route against the full gradient launch instead of the kernel table")
     ap.add_argument("--repeats", type=int, default=3)
     args = ap.parse_args()
     import torch
@@ -90,8 +147,8 @@ def main():
     be = importlib.import_module("code-robchar_amd.backend")
     dev = be.compute_device()
     C, K = 100, 10000
-    if args.philox:
-        text = philox_leg(args, be, dev, C, K)
+    if args.philox or args.listed:
+        text = (listed_leg if args.listed else philox_leg)(args, be, dev, C, K)
         print(text, end="")
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

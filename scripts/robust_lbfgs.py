@@ -3,13 +3,17 @@
 `randHset_constructor`, value AND analytic gradient from one kernel launch per evaluation
 (`noise_model_base.fidelity_ss_av_grad`) - what the reference's qnewton.py does on the CPU with its block-expm gradient.
 
-    python scripts/robust_lbfgs.py [--row 0] [--sigma 0.05] [--maxiter 30] [--train 1000] [--draws set|philox] [--risk 0.0]
+    python scripts/robust_lbfgs.py [--row 0] [--sigma 0.05] [--maxiter 30] [--train 1000] [--draws set|philox] [--risk 0.0 | --cvar ALPHA]
 
 --draws philox: no training set is materialised - the gradient kernel generates `train` counter-based draws per evaluation itself
 (`noise_model_base.fidelity_moments_philox`, shared draws at a fixed seed and offset: common random numbers, so the objective is
 a deterministic smooth function of the controller, as L-BFGS-B needs) and the objective is the risk-averse
 1 - mean F + risk * std F, value and gradient still from one launch.  The test figure then comes from 10 000 draws of the same
 stream behind the training draws.
+--cvar ALPHA (with --draws philox; exclusive with --risk): the tail objective 1 - CVaR_ALPHA F - one minus the mean of the worst
+ALPHA * train draws - from `noise_model_base.fidelity_cvar_philox` (a fidelity launch over all draws, the selection on the
+device, a gradient launch over the selected draws only), same shared draws.  Piecewise smooth: the gradient is exact wherever
+the tail set is locally constant.
 
 Prints value, gradient norm and launches per iteration; `run()` returns the trace for callers (tests)."""
 import argparse
@@ -24,12 +28,18 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def run(row=0, sigma=0.05, maxiter=30, train=1000, pair="0-6", verbose=True, draws="set", risk=0.0, seed=0x5EED0010):
+def run(row=0, sigma=0.05, maxiter=30, train=1000, pair="0-6", verbose=True, draws="set", risk=0.0, seed=0x5EED0010, cvar=None):
     from scipy.optimize import minimize
     if draws not in ("set", "philox"):
         raise ValueError("draws must be 'set' or 'philox'")
     if draws == "set" and risk != 0.0:
         raise ValueError("a risk term needs the moment sums of the kernel that generates its draws: draws='philox'")
+    if cvar is not None and risk != 0.0:
+        raise ValueError("cvar and risk are two objectives: give one of them")
+    if cvar is not None and draws != "philox":
+        raise ValueError("the CVaR objective needs the kernels that generate their draws: draws='philox'")
+    if cvar is not None and not (0.0 < cvar <= 1.0):
+        raise ValueError("cvar: alpha in (0, 1]")
     noise = importlib.import_module("code-robchar_amd.noise")
     z = np.load(os.path.join(ROOT, "tests", "golden", "lbfgs_n7.npz"))
     x0 = np.array(z["ctrl_" + pair][row], dtype=np.float64)
@@ -40,6 +50,9 @@ def run(row=0, sigma=0.05, maxiter=30, train=1000, pair="0-6", verbose=True, dra
 
     def risk_objective(x, n_draws, offset):
         """(1 - fav + risk std, its gradient, fav, std) over `n_draws` shared draws of stream `seed` from element `offset` on"""
+        if cvar is not None:                        # (1 - CVaR, its gradient, CVaR, value at risk)
+            t = nm.fidelity_cvar_philox(np.asarray(x, dtype=np.float64)[None], n_draws, seed, cvar, sigma=sigma, offset=offset, shared=True)
+            return 1.0 - float(t["cvar"][0]), -t["grad_cvar"][0], float(t["cvar"][0]), float(t["var"][0])
         m = nm.fidelity_moments_philox(np.asarray(x, dtype=np.float64)[None], n_draws, seed, sigma=sigma, offset=offset, shared=True)
         return (1.0 - float(m["fav"][0]) + risk * float(m["std"][0]), -m["grad_fav"][0] + risk * m["grad_std"][0],
                 float(m["fav"][0]), float(m["std"][0]))
@@ -79,9 +92,9 @@ def run(row=0, sigma=0.05, maxiter=30, train=1000, pair="0-6", verbose=True, dra
     out = {"x0": x0, "x": res.x, "start": start[0], "final": final[0], "final_grad": final[1], "trace": trace,
            "launches": launches[0], "test_final": test_final, "model": nm, "train_set": train_set}
     if philox:
-        out.update(test_fav=test_fav, test_std=test_std, seed=seed, risk=risk)
+        out.update(test_fav=test_fav, test_std=test_std, seed=seed, risk=risk, cvar=cvar)       # (cvar: test_fav = CVaR, test_std = VaR)
     if verbose:
-        print(f"final     {'1 - F + risk std' if philox else '1 - F'} = {final[0]:.10f} (train)  {out['test_final']:.10f} (test)  after {launches[0]} launches, "
+        print(f"final     {'1 - CVaR' if cvar is not None else '1 - F + risk std' if philox else '1 - F'} = {final[0]:.10f} (train)  {out['test_final']:.10f} (test)  after {launches[0]} launches, "
               f"{len(trace)} iterations")
     return out
 
@@ -94,6 +107,8 @@ if __name__ == "__main__":
     ap.add_argument("--train", type=int, default=1000)
     ap.add_argument("--pair", default="0-6", choices=("0-6", "0-3"))
     ap.add_argument("--draws", default="set", choices=("set", "philox"))
-    ap.add_argument("--risk", type=float, default=0.0)
+    goal = ap.add_mutually_exclusive_group()
+    goal.add_argument("--risk", type=float, default=0.0)
+    goal.add_argument("--cvar", type=float, default=None, metavar="ALPHA")
     args = ap.parse_args()
-    run(args.row, args.sigma, args.maxiter, args.train, args.pair, draws=args.draws, risk=args.risk)
+    run(args.row, args.sigma, args.maxiter, args.train, args.pair, draws=args.draws, risk=args.risk, cvar=args.cvar)
