@@ -28,7 +28,7 @@ EXPORTS = (
     "rc_mc_fidelity_grad_f64_async", "rc_mc_fidelity_grad_f64", "rc_stats_grad_general_tiles",
     "rc_mc_fidelity_sens_f64_async", "rc_mc_fidelity_sens_f64", "rc_stats_sens_general_tiles",
     "rc_mc_fidelity_sens_philox_f64_async", "rc_mc_fidelity_grad_philox_f64_async",
-    "rc_mc_fidelity_grad_listed_f64_async",
+    "rc_mc_fidelity_grad_listed_f64_async", "rc_tail_select_len", "rc_tail_select_f64_async",
 )
 
 RC_KERNEL_AUTO, RC_KERNEL_TRIDIAG_QL, RC_KERNEL_JACOBI, RC_KERNEL_TRIDIAG_ADJ, RC_KERNEL_EXPM, RC_KERNEL_RING_HH = 0, 1, 2, 3, 4, 5
@@ -160,6 +160,9 @@ def load():
     lib.rc_mc_fidelity_sens_philox_f64_async.argtypes = [i, vp, i, i, i, dp, dp, dp, ull, ull, dbl, dp, ll, ll, dp, dp, dp]
     lib.rc_mc_fidelity_grad_philox_f64_async.argtypes = [i, vp, i, i, i, dp, dp, dp, ull, ull, dbl, dp, i, ll, ll, dp, dp, dp, dp]
     lib.rc_mc_fidelity_grad_listed_f64_async.argtypes = [i, vp, i, i, i, dp, dp, dp, ull, ull, dbl, dp, i, ll, ll, vp, dp, ll, dp, dp, dp]
+    lib.rc_tail_select_len.argtypes = [ll, dbl]
+    lib.rc_tail_select_len.restype = ll
+    lib.rc_tail_select_f64_async.argtypes = [i, vp, dp, ll, ll, dbl, vp, dp, dp]
     _lib = lib
     return lib
 

@@ -641,6 +641,67 @@ def mc_fidelity_grad_listed(controllers, n_draws: int, listed, weights=None, *, 
     return res
 
 
+TAIL_SELECT_OUTPUTS = ("list", "weight", "var")
+
+
+def tail_select_len(n_draws: int, alpha: float) -> int:
+    """m = min(K, ceil(alpha K)) as the library computes it (`rc_tail_select_len`, host only)."""
+    m = int(_lib.load().rc_tail_select_len(int(n_draws), float(alpha)))
+    if m < 0:
+        raise ValueError("alpha must be in (0, 1] and n_draws in 0 .. 2^31 - 1")
+    return m
+
+
+def tail_select(fid, alpha: float, want=TAIL_SELECT_OUTPUTS, device=None):
+    """The lower tail of every row of `fid` (C, K), selected on the GPU in one launch (`rc_tail_select_f64_async`): dict of
+
+        "list"   (C, m) int32     m = min(K, ceil(alpha K)): the indices of the m smallest values of the row under the order
+                                  (value, index) - ties to the lower index -, in ascending index order,
+        "weight" (C, m) float64   1 / (alpha K), and (alpha K - (m - 1)) / (alpha K) on the m-th smallest element,
+        "var"    (C,)   float64   the m-th smallest value (the value at risk),
+
+    the entries named in `want` ("list" always): the bits of `noise.tail_weights` (NumPy route), which is the definition.  -0.0
+    and +0.0 tie; a row with a NaN gives -1 / 0.0 / NaN.  A float64 torch CUDA tensor in: torch tensors on its device, enqueued on
+    the current stream, no host synchronisation.  A NumPy array in: uploaded (to `device`), NumPy arrays out."""
+    alpha = float(alpha)
+    if not (0.0 < alpha <= 1.0):
+        raise ValueError("alpha must be in (0, 1]")
+    want = tuple(want)
+    if any(w not in TAIL_SELECT_OUTPUTS for w in want):
+        raise ValueError(f"want: a subset of {TAIL_SELECT_OUTPUTS}, got {want}")
+    if fid.ndim != 2:
+        raise ValueError("fid: expected (C, K)")
+    C, K = (int(v) for v in fid.shape)
+    if K == 0:
+        raise ValueError("fid: K must be positive")
+    if K > 2 ** 31 - 1:
+        raise ValueError("fid: K must be at most 2^31 - 1")
+    lib = _lib.load()
+    _lib.require_gpu()
+    import torch
+    host = not _is_torch(fid)
+    if host:
+        dev = compute_device() if device is None else torch.device("cuda", device_index(device))
+        fid = torch.from_numpy(np.ascontiguousarray(fid, dtype=np.float64)).to(dev)
+    elif not (fid.is_cuda and fid.dtype == torch.float64):
+        raise ValueError("fid must be a float64 CUDA tensor (or a NumPy array, which is uploaded)")
+    fid = fid.contiguous()
+    dev = fid.device
+    m = tail_select_len(K, alpha)
+    res = {"list": torch.empty((C, m), dtype=torch.int32, device=dev)}
+    if "weight" in want:
+        res["weight"] = torch.empty((C, m), dtype=torch.float64, device=dev)
+    if "var" in want:
+        res["var"] = torch.empty((C,), dtype=torch.float64, device=dev)
+    ptr = lambda k: ctypes.c_void_p(res[k].data_ptr()) if k in res else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.rc_tail_select_f64_async(dev.index or 0, ctypes.c_void_p(stream), ctypes.c_void_p(fid.data_ptr()), C, K, alpha,
+                                            ptr("list"), ptr("weight"), ptr("var")))
+    if host:
+        return {k: v.cpu().numpy() for k, v in res.items()}
+    return res
+
+
 def mc_fidelity_directional(controllers, idx, ab, nspin: int, inspin: int, outspin: int, n_draws: int, h0_diag=None,
                             h0_offdiag=None, out=None):
     """Fidelities of `directional_perturbation` samples straight from (direction index, two normals) per sample

@@ -23,6 +23,8 @@
 //   reduce_kernel            one workgroup per controller: RIM_1, std, min, Q(thr) for the centre / DKW-upper /
 //                            DKW-lower variants in two passes over the K fidelities (fixed summation order).
 //   sort_*_kernel            row sort for the ECDF: merge sort in LDS (K <= 16384), chunked bitonic network above.
+//   tail_select_kernel       one workgroup per row: list, CVaR weights and value at risk of the row's lower tail by a radix
+//                            select over an order-preserving key (no sort), compacted in index order.
 //   philox_normal_kernel     counter-based Gaussian draws for sample spaces too large to draw on the host.
 //
 // Roofline: algorithmic HBM traffic is 24 N + 8 bytes per sample; the kernel is bound by
@@ -47,6 +49,7 @@
 #include "hermitian_core.h"
 #include "csym_core.h"
 #include "sort_core.h"
+#include "select_core.h"
 #include "legacy_rng_core.h"
 #include "mt19937_jump_poly.h"
 #include "ws_plan.h"
@@ -99,6 +102,7 @@ typedef __attribute__((address_space(3))) void* rc_lptr_t;
 #include "k_fidelity_chain.inc.h"
 #include "k_fidelity_dense.inc.h"
 #include "k_reduce_sort.inc.h"
+#include "k_tail_select.inc.h"
 #include "k_draws.inc.h"
 #include "k_fidelity_philox.inc.h"
 #include "k_directional.inc.h"
@@ -1729,6 +1733,61 @@ int rc_mc_fidelity_grad_listed_f64_async(int device, void* stream, int N, int in
     p.L = L;
     return launch_with_part(s, p, sum_out_dev != nullptr, N + 2, "rc_grad_listed_launch",
                             [&] { return rc_grad_listed_launch(N, (void*)s, &p, sum_out_dev); });
+}
+
+// m = min(K, ceil(alpha K)) and the two CVaR weights, in double precision and in the order noise.tail_weights computes them
+static bool tail_plan(long long K, double alpha, long long* m, double* w_body, double* w_last) {
+    if (!(alpha > 0.0 && alpha <= 1.0) || K < 0 || K > 0x7fffffffLL) return false;
+    const double ak = alpha * (double)K;
+    const long long up = (long long)ceil(ak);
+    *m = up < K ? up : K;
+    *w_body = 1.0 / ak;
+    *w_last = (ak - (double)(*m - 1)) / ak;
+    return true;
+}
+
+long long rc_tail_select_len(long long K, double alpha) {
+    long long m;
+    double w_body, w_last;
+    if (!tail_plan(K, alpha, &m, &w_body, &w_last)) return -1;
+    return m;
+}
+
+int rc_tail_select_f64_async(int device, void* stream, const double* fid_dev, long long C, long long K, double alpha,
+                             int* list_out_dev, double* weight_out_dev, double* var_out_dev) {
+    if (!(alpha > 0.0 && alpha <= 1.0)) return fail(RC_EINVAL, "alpha must be in (0, 1]");
+    if (C < 0 || K < 0) return fail(RC_EINVAL, "C and K must be non-negative");
+    if (K > 0x7fffffffLL) return fail(RC_EINVAL, "K must be at most 2^31 - 1");
+    if (C == 0 || K == 0) return RC_OK;
+    if (!fid_dev || !list_out_dev) return fail(RC_EINVAL, "NULL array pointer (fid, list_out)");
+    if (C > 0x7fffffffLL) return fail(RC_EINVAL, "too many rows for one launch");
+    TailParams p{};
+    tail_plan(K, alpha, &p.m, &p.w_body, &p.w_last);
+    p.fid = fid_dev;
+    p.C = C;
+    p.K = K;
+    p.list = list_out_dev;
+    p.weight = weight_out_dev;
+    p.var = var_out_dev;
+    RC_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)C), wgrid((unsigned)((C + 3) / 4));
+    if (K <= 128)                                         // short rows: one wave per row (the route follows K alone)
+        hipLaunchKernelGGL(tail_select_rows_wave_kernel<2>, wgrid, dim3(256), 0, s, p);
+    else if (K <= 512)
+        hipLaunchKernelGGL(tail_select_rows_wave_kernel<8>, wgrid, dim3(256), 0, s, p);
+    else if (K <= kWaveRowMaxK)
+        hipLaunchKernelGGL(tail_select_rows_wave_kernel<kWaveRowMaxK / 64>, wgrid, dim3(256), 0, s, p);
+    else if (K <= (long long)kRedCache * 128)             // the thread count follows K alone, as in enqueue_reduce
+        hipLaunchKernelGGL((tail_select_kernel<128, kRedCache, true>), grid, dim3(128), 0, s, p);
+    else if (K <= (long long)kRedCache * 256)
+        hipLaunchKernelGGL((tail_select_kernel<256, kRedCache, true>), grid, dim3(256), 0, s, p);
+    else if (K <= (long long)kRedCache * 512)
+        hipLaunchKernelGGL((tail_select_kernel<512, kRedCache, true>), grid, dim3(512), 0, s, p);
+    else
+        hipLaunchKernelGGL((tail_select_kernel<512, kSelLongU, false>), grid, dim3(512), 0, s, p);
+    RC_HIP_CHECK(hipGetLastError());
+    return RC_OK;
 }
 
 int rc_mc_fidelity_philox_f64_async(int device, void* stream, int kernel, int N, int in, int out, const double* h0_diag,

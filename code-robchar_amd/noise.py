@@ -78,6 +78,43 @@ def moments_from_sums(mean, moment):
     return {"fav": fav, "grad_fav": grad_fav, "var": var, "grad_var": grad_var, "std": std, "grad_std": grad_std}
 
 
+# Row lengths at which a GPU tensor goes through `backend.tail_select` (the HIP selection kernel) instead of the torch sort: every
+# row length ("Tail selection kernel", has the timing of both routes per shape).
+def _tail_select_routed(K: int) -> bool:
+    return True
+
+
+def _tail_plan(fid, alpha):
+    alpha = float(alpha)
+    if not (0.0 < alpha <= 1.0):
+        raise ValueError("alpha must be in (0, 1]")
+    if fid.ndim != 2:
+        raise ValueError("fid: expected (C, K)")
+    K = int(fid.shape[1])
+    if K == 0:
+        raise ValueError("fid: K must be positive")
+    ak = alpha * K
+    m = min(K, int(np.ceil(ak)))
+    return m, 1.0 / ak, (ak - (m - 1)) / ak
+
+
+def _tail_weights_torch(fid, alpha: float):
+    """`tail_weights` of a torch tensor by torch's stable sort (any device): the route GPU tensors took before the selection
+    kernel; kept for CPU tensors, for the timing (scripts/grad_bench.py --select) and as a cross-check."""
+    import torch
+    m, w_body, w_last = _tail_plan(fid, alpha)
+    order = torch.argsort(fid, dim=1, stable=True)[:, :m]
+    last = order[:, m - 1:m]
+    listed = torch.sort(order, dim=1).values
+    weights = torch.full(listed.shape, w_body, dtype=torch.float64, device=fid.device)
+    weights[listed == last] = w_last
+    bad = torch.isnan(fid).any(dim=1, keepdim=True).expand_as(listed)
+    listed = listed.to(torch.int32)
+    listed[bad] = -1
+    weights[bad] = 0.0
+    return listed, weights
+
+
 def tail_weights(fid, alpha: float):
     """List and weights of the lower tail of each row of `fid` (C, K) for `backend.mc_fidelity_grad_listed`: with them its "sum"
     row is (CVaR_alpha F, d CVaR_alpha / dx) of the row's empirical distribution (Rockafellar - Uryasev; the gradient holds
@@ -89,30 +126,15 @@ def tail_weights(fid, alpha: float):
                                   empirical distribution; every row sums to 1
 
     alpha in (0, 1]: alpha = 1 gives every index with weight 1 / K (the mean), alpha K < 1 the minimum with weight 1.  A row
-    with a NaN in it gives empty slots (-1) with weight 0."""
-    alpha = float(alpha)
-    if not (0.0 < alpha <= 1.0):
-        raise ValueError("alpha must be in (0, 1]")
-    if fid.ndim != 2:
-        raise ValueError("fid: expected (C, K)")
-    K = int(fid.shape[1])
-    if K == 0:
-        raise ValueError("fid: K must be positive")
-    ak = alpha * K
-    m = min(K, int(np.ceil(ak)))
-    w_body, w_last = 1.0 / ak, (ak - (m - 1)) / ak
+    with a NaN in it gives empty slots (-1) with weight 0.
+    The NumPy route below is the definition.  A float64 torch tensor on a GPU is selected by the HIP kernel behind
+    `backend.tail_select` (same bits, one launch, no sort); a CPU tensor takes torch's stable sort."""
+    m, w_body, w_last = _tail_plan(fid, alpha)
     if backend._is_torch(fid):
-        import torch
-        order = torch.argsort(fid, dim=1, stable=True)[:, :m]
-        last = order[:, m - 1:m]
-        listed = torch.sort(order, dim=1).values
-        weights = torch.full(listed.shape, w_body, dtype=torch.float64, device=fid.device)
-        weights[listed == last] = w_last
-        bad = torch.isnan(fid).any(dim=1, keepdim=True).expand_as(listed)
-        listed = listed.to(torch.int32)
-        listed[bad] = -1
-        weights[bad] = 0.0
-        return listed, weights
+        if fid.is_cuda and str(fid.dtype) == "torch.float64" and _tail_select_routed(int(fid.shape[1])):
+            res = backend.tail_select(fid, alpha, want=("list", "weight"))
+            return res["list"], res["weight"]
+        return _tail_weights_torch(fid, alpha)
     fid = np.asarray(fid, dtype=np.float64)
     order = np.argsort(fid, axis=1, kind="stable")[:, :m]
     last = order[:, m - 1:m]
@@ -370,8 +392,8 @@ class noise_model_base:
         """CVaR_alpha of the fidelity - the mean of the worst alpha K of `n_draws` counter-based draws per controller - with its
         gradient with respect to the controller: {"cvar" (C,), "grad_cvar" (C, N+1), "var" (C,)}, NumPy arrays.  Three launches,
         nothing per sample leaves the device: the fidelities of all K draws (`backend.mc_fidelity_philox`, the mixed-precision
-        kernel), `tail_weights` on the device, and ONE `backend.mc_fidelity_grad_listed` launch over the selected ceil(alpha K)
-        draws with want=("sum",).  "cvar" is that launch's own weighted sum, so value and gradient come from one evaluation;
+        kernel), ONE selection launch (`backend.tail_select`: list, weights, value at risk), and ONE
+        `backend.mc_fidelity_grad_listed` launch over the selected ceil(alpha K) draws with want=("sum",).  "cvar" is that launch's own weighted sum, so value and gradient come from one evaluation;
         "var" - the value at risk - is the largest selected fidelity.  The gradient is that of the empirical CVaR where the tail
         set is locally constant (almost everywhere).  A NaN row gives NaN.  alpha = 1: the mean and its gradient.
         `sigma`, `offset`, `shared` and the restrictions (chain topology, real static couplings): as `fidelity_moments_philox`."""
@@ -407,10 +429,14 @@ class noise_model_base:
         else:                                      # (one draw set, one scale per row: no fidelity-only kernel takes that)
             fid = backend.mc_fidelity_grad_philox(ctrl, K, N, self.inspin, self.outspin, seed, offset=offset, sigma=sigma, shared=True,
                                                   h0_diag=diag, h0_offdiag=off, want=("fid",))["fid"]
-        listed, weights = tail_weights(fid, alpha)
+        if _tail_select_routed(K):                 # list, weights and value at risk from ONE selection launch
+            sel = backend.tail_select(fid, alpha)
+            listed, weights, var = sel["list"], sel["weight"], sel["var"]
+        else:
+            listed, weights = _tail_weights_torch(fid, alpha)
+            var = torch.gather(fid, 1, listed.clamp(min=0).long()).max(dim=1).values   # (a NaN row gathers NaN)
         res = backend.mc_fidelity_grad_listed(ctrl, K, listed, weights, nspin=N, inspin=self.inspin, outspin=self.outspin, seed=seed,
                                               offset=offset, sigma=sigma, shared=shared, h0_diag=diag, h0_offdiag=off, want=("sum",))
-        var = torch.gather(fid, 1, listed.clamp(min=0).long()).max(dim=1).values       # (a NaN row gathers NaN)
         total = res["sum"].cpu().numpy()
         nan = np.isnan(ctrl.cpu().numpy()).any(axis=1)
         var = var.cpu().numpy().copy()

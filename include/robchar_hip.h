@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 11      /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 12      /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -62,7 +62,8 @@ extern "C" {
                                      (additive);
                                   9: + rc_mc_fidelity_sens_philox_f64_async (additive);
                                   10: + rc_mc_fidelity_grad_philox_f64_async (additive);
-                                  11: + rc_mc_fidelity_grad_listed_f64_async (additive) */
+                                  11: + rc_mc_fidelity_grad_listed_f64_async (additive);
+                                  12: + rc_tail_select_len, rc_tail_select_f64_async (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -285,7 +286,8 @@ int rc_mc_fidelity_grad_philox_f64_async(int device, void* stream, int N, int in
 
 /* (ABI 11) rc_mc_fidelity_grad_philox_f64_async over a caller-chosen LIST of each row's K draws, with caller-chosen weights on
  * the row sums:   sum_out[c] = sum_s  w[c][s] * (F, dF/dx_0 .. dF/dx_N)(c, list[c][s]),   s = 0 .. L - 1.
- * Tail weights on the worst alpha K draws give CVaR_alpha and its gradient (noise.tail_weights), softmax weights the entropic
+ * Tail weights on the worst alpha K draws give CVaR_alpha and its gradient (noise.tail_weights; on the device, without
+ * torch: rc_tail_select_f64_async below, which writes list_dev and weight_dev from the fidelities), softmax weights the entropic
  * risk, a smoothed step's derivative a yield; repeated indices (bootstrap resamples) are allowed.  Only the listed samples are
  * computed.  Slot s of row c is sample (c, k = list_dev[c][s]) of the stream conventions above (`shared_draws`, `offset`, `sigma` /
  * sigma_rows_dev[c]): offset + ((c K + k) N + i) 3 + s', shared draws offset + (k N + i) 3 + s'.  A value outside 0 .. K - 1 is an
@@ -311,6 +313,31 @@ int rc_mc_fidelity_grad_listed_f64_async(int device, void* stream, int N, int in
                                          const double* sigma_rows_dev, int shared_draws, long long C, long long K,
                                          const int* list_dev, const double* weight_dev, long long L,
                                          double* fid_out_dev, double* grad_out_dev, double* sum_out_dev);
+
+/* (ABI 12) The lower tail of every row of a fidelity table, selected on the device: the list and the weights that make
+ * rc_mc_fidelity_grad_listed_f64_async's sum_out the CVaR_alpha of the row and its gradient, and the value at risk.  The definition
+ * is noise.tail_weights (NumPy route); every output carries its bits.
+ *     m = rc_tail_select_len(K, alpha) = min(K, ceil(alpha K))     host only, no HIP call; -1 on bad arguments (alpha not in (0, 1]
+ *                                                                  or NaN, K negative or above 2^31 - 1).
+ * The host computes, in double precision and in exactly this order,   ak = alpha * K,   m = min(K, (long long)ceil(ak)),
+ * w_body = 1.0 / ak,   w_last = (ak - (m - 1)) / ak.   Outputs for row c of fid_dev [C][K]:
+ *     list_out   [C][m] int32   the indices of the m smallest values of the row under the order (value, index): ties go to the
+ *                               lower index, as in NumPy's stable sort.  They are written in ascending index order.
+ *     weight_out [C][m]         optional (NULL = not wanted): w_body everywhere, and w_last on the slot that holds the m-th smallest
+ *                               element in that order.  With ties at the threshold, that is the selected tied element with the
+ *                               highest index.
+ *     var_out    [C]            optional: the m-th smallest value itself.
+ * -0.0 and +0.0 are equal (NumPy treats them so), and the index breaks the tie.  A row containing any NaN gives list = -1,
+ * weight = 0.0, var = NaN.  No sort: a radix select over an order-preserving 64-bit key and a compaction in index order, one
+ * workgroup per row (one wave for rows of up to 2048 values), no workspace, integer counts only - same inputs, same bits, and the
+ * same on every route.
+ * Argument checks before any HIP call: alpha not in (0, 1], or NaN: RC_EINVAL; C or K negative: RC_EINVAL; K > 2^31 - 1: RC_EINVAL;
+ * C or K = 0: RC_OK, nothing written; fid_dev or list_out_dev NULL: RC_EINVAL.  Enqueue-only: device pointers, launched on `stream`,
+ * no allocation, no synchronisation; may be captured.  The three-call CVaR sequence of a client without torch:
+ * rc_mc_fidelity_philox_f64_async -> rc_tail_select_f64_async -> rc_mc_fidelity_grad_listed_f64_async. */
+long long rc_tail_select_len(long long K, double alpha);
+int rc_tail_select_f64_async(int device, void* stream, const double* fid_dev, long long C, long long K, double alpha,
+                             int* list_out_dev, double* weight_out_dev, double* var_out_dev);
 
 /* (ABI 6) 1 when the kernel above is the faster of the two bit-identical routes for this geometry (N <= 13, or N = 14 with
  * {in, out} = {0, N-1}), else 0; 0 everywhere when ROBCHAR_PHILOX_FUSED=0 is in the environment (read per call).  The ONE

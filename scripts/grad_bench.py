@@ -18,7 +18,16 @@ mean + moment.  The routes alternate in one process, `--launches` launches after
 draws (`mc_fidelity_philox`) + the selection on the device (`noise.tail_weights`) + the listed launch over the selected alpha K
 (`mc_fidelity_grad_listed`, sum only), alpha = 0.1 and 0.01, N = 5, 7, 10, 12 at 100 x 10 000, sigma = 0.05, same alternation.
 
-    python scripts/grad_bench.py --listed [--out profiles/grad_listed_bench.txt]"""
+    python scripts/grad_bench.py --listed [--out profiles/grad_listed_bench.txt]
+
+Its last three columns split (b) at alpha = 0.1 into its launches: fidelity, selection (`backend.tail_select`), listed.
+
+--select times the selection alone on a table of fidelities (N = 7, sigma = 0.05): (a) the torch route it replaces
+(`noise._tail_weights_torch` + the gather / max of the value at risk), (b) `backend.tail_select`, (c) `reduce_metrics` through its
+standalone route on the same table - the floor: it reads each row once.  100 x 10 000 and 1000 x 10 000 at alpha = 0.1 and 0.01,
+11 000 x 100 at alpha = 0.1, 1000 x 100 000 at alpha = 0.01 (a tenth of the launches: its torch sort takes ~0.1 s).
+
+    python scripts/grad_bench.py --select [--out profiles/tail_select_bench.txt]"""
 import argparse
 import importlib
 import os
@@ -93,7 +102,8 @@ def listed_leg(args, be, dev, C, K):
              f"(mc_fidelity_grad_philox, mean only), {C} x {K}, sigma = {sigma}, {args.launches} launches after {args.warmup}, routes "
              f"alternated, {args.repeats} repeats (min .. max, us per evaluation), HIP events",
              f"# device: {torch.cuda.get_device_name(dev)}",
-             "# N  in out | (a) full launch us | " + " | ".join(f"(b) alpha = {al} us | (b)/(a)" for al in alphas) + " (of the minima)"]
+             "# N  in out | (a) full launch us | " + " | ".join(f"(b) alpha = {al} us | (b)/(a)" for al in alphas) + " (of the minima)"
+             f" | the launches of (b) at alpha = {alphas[0]} alone: fidelity us | selection us | listed us (minima)"]
     work = {w[0]: w for w in (highfid_workload(cid, C=C) for cid in (2, 3, 5))}
     work[12] = (12, 0, 11, cc.deloc_ctrl(np.random.default_rng(12), C, 12, 0.5), None)
 
@@ -123,13 +133,78 @@ def listed_leg(args, be, dev, C, K):
             be.mc_fidelity_grad_listed(ct, K, listed, weights, nspin=N, inspin=a, outspin=b, seed=seed, sigma=sigma, h0_diag=h0,
                                        want=("sum",))
 
-        ta, tb = [], {al: [] for al in alphas}
+        ta, tb, tf, ts, tl = [], {al: [] for al in alphas}, [], [], []
+        be.mc_fidelity_philox(ct, K, N, a, b, seed, sigma=sigma, h0_diag=h0, out=fid)
+        sel = be.tail_select(fid, alphas[0], want=("list", "weight"))
         for _ in range(args.repeats):
             ta.append(timed_calls(lambda: be.mc_fidelity_grad_philox(ct, K, N, a, b, seed, sigma=sigma, h0_diag=h0, want=("mean",))))
             for al in alphas:
                 tb[al].append(timed_calls(lambda: tail(al)))
-        lines.append(f"{N:3d} {a:3d} {b:3d} | {spread(ta)} | " + " | ".join(f"{spread(tb[al])} | {min(tb[al]) / min(ta):5.2f}" for al in alphas))
+            tf.append(timed_calls(lambda: be.mc_fidelity_philox(ct, K, N, a, b, seed, sigma=sigma, h0_diag=h0, out=fid)))
+            ts.append(timed_calls(lambda: be.tail_select(fid, alphas[0], want=("list", "weight"))))
+            tl.append(timed_calls(lambda: be.mc_fidelity_grad_listed(ct, K, sel["list"], sel["weight"], nspin=N, inspin=a, outspin=b,
+                                                                     seed=seed, sigma=sigma, h0_diag=h0, want=("sum",))))
+        lines.append(f"{N:3d} {a:3d} {b:3d} | {spread(ta)} | " + " | ".join(f"{spread(tb[al])} | {min(tb[al]) / min(ta):5.2f}" for al in alphas)
+                     + f" | {min(tf):9.1f} | {min(ts):9.1f} | {min(tl):9.1f}")
         print(lines[-1], flush=True)
+    return "\n".join(lines) + "\n"
+
+
+def select_leg(args, be, dev):
+    import torch
+    from conftest import highfid_workload
+    noise = importlib.import_module("code-robchar_amd.noise")
+    sigma, seed = 0.05, 7
+    shapes = ((100, 10_000, (0.1, 0.01), 1), (1000, 10_000, (0.1, 0.01), 1), (11_000, 100, (0.1,), 1), (1000, 100_000, (0.01,), 10))
+    lines = [f"# tail selection of a (C, K) fidelity table (N = 7, sigma = {sigma}): (a) torch route (stable argsort + sort + masks + gather / "
+             f"max), (b) backend.tail_select, (c) reduce_metrics, standalone route, no thresholds (the floor: one read of every row); "
+             f"{args.launches} launches after {args.warmup} (the last shape: a tenth of both), routes alternated, {args.repeats} repeats "
+             "(min .. max, us per call), HIP events",
+             f"# device: {torch.cuda.get_device_name(dev)}",
+             "#     C       K  alpha | (a) torch us | (b) tail_select us | (c) reduce us | (b)/(a) | (b)/(c) (of the minima) | table MB"]
+
+    def spread(v):
+        return f"{min(v):10.1f} .. {max(v):10.1f}"
+
+    for C, K, alphas, fewer in shapes:
+        N, a, b, ctrl, h0 = highfid_workload(3, C=C)
+        ct = torch.from_numpy(ctrl).to(dev)
+        try:
+            fid = be.mc_fidelity_philox(ct, K, N, a, b, seed, sigma=sigma, h0_diag=h0)
+            noise._tail_weights_torch(fid, alphas[0])                # (does the sort's workspace fit?)
+            torch.cuda.synchronize(dev)
+        except (RuntimeError, MemoryError) as exc:
+            lines.append(f"{C:7d} {K:7d}: the table and the torch sort's temporaries do not fit: {type(exc).__name__}")
+            print(lines[-1], flush=True)
+            continue
+        warmup, launches = max(1, args.warmup // fewer), max(1, args.launches // fewer)
+
+        def timed_calls(fn):
+            for _ in range(warmup):
+                fn()
+            torch.cuda.synchronize(dev)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(launches):
+                fn()
+            e1.record()
+            torch.cuda.synchronize(dev)
+            return e0.elapsed_time(e1) * 1e3 / launches
+
+        def old(alpha):
+            listed, weights = noise._tail_weights_torch(fid, alpha)
+            return torch.gather(fid, 1, listed.clamp(min=0).long()).max(dim=1).values
+
+        for alpha in alphas:
+            ta, tb, tc = [], [], []
+            for _ in range(args.repeats):
+                ta.append(timed_calls(lambda: old(alpha)))
+                tb.append(timed_calls(lambda: be.tail_select(fid, alpha)))
+                tc.append(timed_calls(lambda: be.reduce_metrics(fid, q_thresholds=(), overlapped=False)))
+            lines.append(f"{C:7d} {K:7d} {alpha:6.2f} | {spread(ta)} | {spread(tb)} | {spread(tc)} | {min(tb) / min(ta):7.4f} | "
+                         f"{min(tb) / min(tc):6.2f} | {fid.numel() * 8 / 1e6:8.1f}")
+            print(lines[-1], flush=True)
+        del fid
     return "\n".join(lines) + "\n"
 
 
@@ -140,6 +215,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--philox", action="store_true", help="the fused-against-two-kernel leg instead of the kernel table")
     ap.add_argument("--listed", action="store_true", help="the CVaR route against the full gradient launch instead of the kernel table")
+    ap.add_argument("--select", action="store_true", help="the tail selection against the torch route and the reduction instead of the kernel table")
     ap.add_argument("--repeats", type=int, default=3)
     args = ap.parse_args()
     import torch
@@ -147,8 +223,8 @@ def main():
     be = importlib.import_module("code-robchar_amd.backend")
     dev = be.compute_device()
     C, K = 100, 10000
-    if args.philox or args.listed:
-        text = (listed_leg if args.listed else philox_leg)(args, be, dev, C, K)
+    if args.philox or args.listed or args.select:
+        text = select_leg(args, be, dev) if args.select else (listed_leg if args.listed else philox_leg)(args, be, dev, C, K)
         print(text, end="")
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
