@@ -159,7 +159,9 @@ __global__ __launch_bounds__(64, dir_bond_min_waves(N)) void mc_fid_dir_bond_ker
     bool ok = true;
     int extra = 0;
     const bool run = live && !pad;
-    if (run) ok = rc::chain_fidelity_fast<N, MODE>(xg, p.h0.diag, p.h0.off, lg, p.in, p.out, sctab, f, nullptr, &extra);
+    // (AMPLITUDE = false: the end-to-end mode keeps its weights here - with ends_amplitude this kernel needs 9 - 14 registers
+    // more at N = 9 .. 12, at N = 10 a wave of residency, 123 -> 132)
+    if (run) ok = rc::chain_fidelity_fast<N, MODE, false>(xg, p.h0.diag, p.h0.off, lg, p.in, p.out, sctab, f, nullptr, &extra);
     if (extra && lane == 0) atomicAdd(&g_polish_tiles[blockIdx.x & 63u], 1ull);
     unsigned long long badmask = __ballot(run && !ok);
     if (badmask) {                                              // rare: the eigenvector-rows route for those lanes

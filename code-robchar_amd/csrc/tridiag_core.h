@@ -1071,6 +1071,104 @@ RC_HD bool ends_weights(double pe, const double (&lam)[N], double (&w)[N], doubl
     return ok;
 }
 
+// End-to-end FIDELITY without the weights: with chi'_k = prod_{m != k}(lam_k - lam_m), tot = prod_k chi'_k and the
+// cofactor products P_k = prod_{j != k} chi'_j = tot / chi'_k,
+//     F = |sum_k pe / chi'_k exp(-i T lam_k)|^2 = pe^2 |sum_k P_k exp(-i T (lam_k - lam_0))|^2 / tot^2 .
+// Only pe^2 = prod e_i^2 enters - the caller never takes the root of the product of the squares - and the common factors
+// pe and 1 / tot are applied once behind the phase sum instead of to every weight: against ends_weights + the phase loop,
+// N multiplications by pe and N - 1 by the shared reciprocal go, and the reciprocal leaves the critical path of the sum.
+// P_k = (prefix product up to k - 1) * (suffix product from k + 1): the prefixes are the ones the batch inverse forms, the
+// suffix runs along with the peel-off loop, which leaves P_k where chi'_k was (two phases, as in ends_weights + the phase
+// loop: first every P_k, then the sum - written as ONE loop the N = 13, 14 kernels needed a residency step more registers).
+// The phase sum of a batch is scaled by its reciprocal BEFORE it is squared, (re / tot)^2 and not re^2 / tot^2: a P_k
+// reaches 1e150 at a spectral scale of 1e4, its square is out of range.  Batches as in ends_weights (B (N - 1) <= 60:
+// every P_k in range up to that scale; one reciprocal per batch, each batch's sums scaled by its own total), the same range
+// guard on each total; N = 2 and N >= 14: one reciprocal per eigenvalue, as there.
+// A product of squares that underflowed to 0 (several cut bonds) gives F = 0; a sum that is not finite gives a NaN, which
+// the caller's `fid <= 2` sends to the repair route.  `lam`, GAPS, `gap_tol`: as for ends_weights; T: the time (>= 0).
+#ifndef RC_ENDS_AMPLITUDE_MAX_N
+#define RC_ENDS_AMPLITUDE_MAX_N 13
+#endif
+constexpr int kEndsAmplitudeMaxN = RC_ENDS_AMPLITUDE_MAX_N;   // REGISTER limit of the kernels (nothing to do with RC_MIXED_MAX_N): see chain_fidelity_fast
+template <int N, bool GAPS>
+RC_HD bool ends_amplitude(double pe_sq, const double (&lam)[N], double T, const double* sctab, double& fid,
+                          double gap_tol = kDegenerateGapNoMix) {
+    double mingap = 1e300, scale = 1.0;
+    double w[N];                                      // chi'_k, then P_k (N = 2, N >= 14: 1 / chi'_k)
+#pragma unroll
+    for (int k = 0; k < N; ++k) w[k] = 1.0;
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        if (GAPS) scale = fmax(scale, fabs(lam[k]));
+#pragma unroll
+        for (int m = k + 1; m < N; ++m) {
+            const double df = lam[k] - lam[m];
+            if (GAPS) mingap = fmin(mingap, fabs(df));
+            w[k] *= df;
+            w[m] *= -df;
+        }
+    }
+    bool ok = !GAPS || mingap > gap_tol * scale;
+    constexpr bool BATCH = kBatchInverse && N >= 3 && N <= 13;
+    constexpr int B = !BATCH ? N : ((60 / (N - 1)) < 1 ? 1 : (60 / (N - 1)));      // (not batched: one "batch" with total 1)
+    constexpr int NB = (N + B - 1) / B;
+    double rinv[NB];
+    if (BATCH) {
+#pragma unroll
+        for (int k0 = 0; k0 < N; k0 += B) {
+            const int k1 = (k0 + B < N) ? (k0 + B) : N;         // compile-time after unrolling
+            double pre[B];
+            pre[0] = w[k0];
+#pragma unroll
+            for (int k = k0 + 1; k < k1; ++k) pre[k - k0] = pre[k - k0 - 1] * w[k];
+            const double tot = pre[k1 - k0 - 1];
+            ok = ok && (fabs(tot) > 1e-280) && (fabs(tot) < 1e280);
+            rinv[k0 / B] = rcp_full(tot);
+            double suf = 1.0;                                   // prod_{k < j < k1} chi'_j
+#pragma unroll
+            for (int k = k1 - 1; k > k0; --k) {
+                const double wk = w[k];
+                w[k] = (k == k1 - 1) ? pre[k - k0 - 1] : pre[k - k0 - 1] * suf;
+                suf = (k == k1 - 1) ? wk : suf * wk;
+            }
+            w[k0] = suf;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < N; ++k) w[k] = rcp_full(w[k]);
+        rinv[0] = 1.0;
+    }
+    // sum_k P_k exp(-i T (lam_k - lam_0)): N - 1 sincos (theta_0 = 0); the sign of the imaginary part does not reach |.|^2
+    const double Tk = T * kTurnsPerRadian;
+    double re = 0.0, im = 0.0;
+#pragma unroll
+    for (int k0 = 0; k0 < N; k0 += B) {
+        const int k1 = (k0 + B < N) ? (k0 + B) : N;
+        double reb = 0.0, imb = 0.0;
+#pragma unroll
+        for (int k = k0; k < k1; ++k) {
+            if (k == 0) {
+                reb = w[0];
+                continue;
+            }
+            double sk, ck;
+            if (kTableSinCos) sincos_table(Tk * (lam[k] - lam[0]), sctab, sk, ck);
+            else sincos_reduced(T * (lam[k] - lam[0]), sk, ck);
+            reb = (k == k0) ? w[k] * ck : fma(w[k], ck, reb);
+            imb = (k == k0 || k == 1) ? w[k] * sk : fma(w[k], sk, imb);
+        }
+        if (BATCH) {
+            re = (k0 == 0) ? reb * rinv[0] : fma(reb, rinv[k0 / B], re);
+            im = (k0 == 0) ? imb * rinv[0] : fma(imb, rinv[k0 / B], im);
+        } else {
+            re = reb;
+            im = imb;
+        }
+    }
+    fid = pe_sq * fma(re, re, im * im);
+    return ok;
+}
+
 // A-POSTERIORI GUARD of the eigenvalue-only weight modes (round 4).  Whatever route produced them, the weights w_k =
 // Q[out,k] Q[in,k] and the eigenvalues must reproduce the first moments of the matrix itself,
 //     sum_k w_k (lam_k - c)^m = ((H - c I)^m)[out,in],   m = 0, 1, 2,
@@ -1208,18 +1306,25 @@ enum WeightMode {
 // Eigenvalues: the eigenvalue-only modes at 3 <= N <= RC_MIXED_MAX_N take the mixed-precision route (fp32 QL -> fp64 Halley
 // step -> stepping path -> all-fp64 QL for the tile, in that order of escalation; see the block comment at kMixedEig);
 // the rows mode and larger N run the all-fp64 QL (tridiag_ql2_fast).
+// AMPLITUDE = false keeps the end-to-end mode on the weights (the directional kernel: see there).
 // `stamp` is used by diagnostic builds only (-DRC_STAMPS); `extra_steps` (optional) is set to 1 when the tile left the
 // one-step path of the mixed-precision route (rc_stats_polish_tiles).
-template <int N, int MODE, typename LoadG>
+template <int N, int MODE, bool AMPLITUDE = true, typename LoadG>
 RC_HD bool chain_fidelity_fast(const double* x, const double* h0d, const double* h0o, LoadG loadg,
                                int in, int out, const double* sctab, double& fid, long long* stamp = nullptr,
                                int* extra_steps = nullptr) {
     constexpr bool VEC = (MODE == kWeightsRows);
     constexpr bool MIXED = kMixedEig && !VEC && N >= 3 && N <= RC_MIXED_MAX_N;
+    // end-to-end mode: the fidelity straight from the eigenvalues and the product of the SQUARED couplings (ends_amplitude).
+    // The weights are formed as before (ends_weights, pe = the root of that product) where the sum-rule guard is switched on
+    // for this mode - it reads them -, at N >= 14 - with ends_amplitude the N = 14 kernel spills 6 registers and the N = 14
+    // fused-draws kernel goes from 244 to 264, a wave of residency - and for a caller that asks for it (AMPLITUDE = false).
+    constexpr bool AMP = AMPLITUDE && (MODE == kWeightsEnds) && !kSumRuleEnds && N <= kEndsAmplitudeMaxN;
     TriEig<N, VEC ? 2 : 0> s;
     double d0[N], e0sq[N], w[N];               // kWeightsAdjugate / mixed path: original diagonal / squared couplings
     float df[N], ef[N];                        // mixed path: the fp32 copy the QL rotations work on
-    double pe_all = 1.0;                       // product of the couplings between the two sites (all of them: kWeightsEnds)
+    double pe_all = 1.0;                       // product of the couplings between the two sites (all of them: kWeightsEnds;
+                                               // AMP: of their squares)
     const int lo = in < out ? in : out, hi = in < out ? out : in;
 #pragma unroll
     for (int i = 0; i < N; ++i) {
@@ -1249,7 +1354,7 @@ RC_HD bool chain_fidelity_fast(const double* x, const double* h0d, const double*
         double r, rinv;
         sqrt_rsqrt(h, r, rinv);
         s.e[i - 1] = r;
-        if (MODE == kWeightsEnds) pe_all *= s.e[i - 1];
+        if (MODE == kWeightsEnds) pe_all *= AMP ? h : s.e[i - 1];
         if (MODE == kWeightsAdjugate) {
             e0sq[i - 1] = h;
             if (i - 1 >= lo && i - 1 < hi) pe_all *= s.e[i - 1];     // wave-uniform condition
@@ -1273,7 +1378,7 @@ RC_HD bool chain_fidelity_fast(const double* x, const double* h0d, const double*
         e0sq[N - 1] = 0.0;
 #pragma unroll
         for (int i = 0; i < N; ++i) d0[i] = s.d[i];
-        {   // pe = sqrt(prod e^2); the nudge keeps the seed finite when the product underflows (several cut bonds)
+        if (!AMP) {   // pe = sqrt(prod e^2); the nudge keeps the seed finite when the product underflows (several cut bonds)
             double r, rinv;
             sqrt_rsqrt(pe_all + 1e-300, r, rinv);
             pe_all = r;
@@ -1331,7 +1436,8 @@ RC_HD bool chain_fidelity_fast(const double* x, const double* h0d, const double*
             ok = (!need && RC_KEEP_SETTLED) || okql;
             need = (need || !RC_KEEP_SETTLED) && need2;
         }
-        const bool wok = (MODE == kWeightsAdjugate) ? adjugate_weights<N, false>(d0, e0sq, s.d, lo, hi, pe_all, w)
+        const bool wok = AMP ? ends_amplitude<N, false>(pe_all, s.d, fabs(x[N]), sctab, fid)
+                       : (MODE == kWeightsAdjugate) ? adjugate_weights<N, false>(d0, e0sq, s.d, lo, hi, pe_all, w)
                                                     : ends_weights<N, false>(pe_all, s.d, w);
         ok = ok && wok && !need;
     } else {
@@ -1373,23 +1479,27 @@ RC_HD bool chain_fidelity_fast(const double* x, const double* h0d, const double*
         for (int k = 0; k < N; ++k) w[k] = s.z[VEC ? 1 : 0][k] * s.z[0][k];
     } else if (MODE == kWeightsAdjugate) {
         ok = adjugate_weights<N>(d0, e0sq, s.d, lo, hi, pe_all, w) && ok;
+    } else if (AMP) {
+        ok = ends_amplitude<N, true>(pe_all, s.d, fabs(x[N]), sctab, fid) && ok;
     } else {
         ok = ends_weights<N>(pe_all, s.d, w) && ok;
     }
-    // |sum_k w_k exp(-i T lam_k)|^2 is unchanged by the global phase exp(i T lam_0): N-1 sincos instead of N
-    const double T = fabs(x[N]);
-    const double Tk = T * kTurnsPerRadian;
-    double re = w[0], im = 0.0;
+    if (!AMP) {
+        // |sum_k w_k exp(-i T lam_k)|^2 is unchanged by the global phase exp(i T lam_0): N-1 sincos instead of N
+        const double T = fabs(x[N]);
+        const double Tk = T * kTurnsPerRadian;
+        double re = w[0], im = 0.0;
 #pragma unroll
-    for (int k = 1; k < N; ++k) {
-        double sk, ck;
-        if (kTableSinCos) sincos_table(Tk * (s.d[k] - s.d[0]), sctab, sk, ck);
-        else sincos_reduced(T * (s.d[k] - s.d[0]), sk, ck);
-        re = fma(w[k], ck, re);
-        im = fma(-w[k], sk, im);
+        for (int k = 1; k < N; ++k) {
+            double sk, ck;
+            if (kTableSinCos) sincos_table(Tk * (s.d[k] - s.d[0]), sctab, sk, ck);
+            else sincos_reduced(T * (s.d[k] - s.d[0]), sk, ck);
+            re = fma(w[k], ck, re);
+            im = fma(-w[k], sk, im);
+        }
+        fid = fma(re, re, im * im);
     }
-    fid = fma(re, re, im * im);
-    if (MIXED) ok = ok && (fid <= 2.0);             // a NaN (zero Halley denominator) goes to the general path
+    if (MIXED || AMP) ok = ok && (fid <= 2.0);      // a NaN (zero Halley denominator, sums out of range) goes to the general path
     // (the rows mode carries genuine eigenvector rows: it IS the repair route and needs no guard)
     if (kSumRuleGuard && !VEC && (MODE != kWeightsEnds || kSumRuleEnds))
         ok = ok && chain_sum_rules_ok<N, MODE == kWeightsEnds>(w, s.d, hi - lo, gsites, pe_all, MIXED ? (double)scale32 : 0.0);
