@@ -376,8 +376,11 @@ int rc_mc_fidelity_directional_f64_async(int device, void* stream, int N, int in
  *   0: centre  F          1: " upper"  clip(F - dkw_eps, 0, 1)        2: " lower"  clip(F + dkw_eps, 0, 1)
  * (naming of mcsim.py:484-485).  Shapes: rim1/std_/minf [3][C];  q [3][nq][C] = fraction of samples >=
  * q_thresholds[j] (the reference stores the NEGATED value; signs are applied by the host layer).
- * std_ is the population standard deviation (np.std).  NaN rows give NaN (q: 0).
- * sorted_out: NULL, or [C][K] receiving each row sorted ascending (NaN rows copied through); any K (one
+ * std_ is the population standard deviation (np.std).  A row holding ANY NaN - all of it (a padded controller) or a single
+ * value - gives NaN in rim1 / std_ / minf of all three variants.  Its q is the count of the non-NaN values >= threshold over K
+ * (the reference's Q, where NaN counts as below): 0 for a whole-NaN row, not for a row with some NaN.  Inside the two shifted
+ * variants a NaN is clamped to 0, so there - unlike np.clip, which keeps it - it counts against a threshold <= 0.
+ * sorted_out: NULL, or [C][K] receiving each row sorted ascending (a row holding any NaN is copied through unchanged); any K (one
  * launch for K <= 16384, a bitonic network with HBM passes above; internal grow-only workspace).
  * Any output pointer may be NULL to skip it.  nq <= 8.  q_thresholds is a HOST pointer.
  * Summation order: fixed per (K, route) - bitwise reproducible from run to run.  The kernel is chosen by K (one workgroup of
