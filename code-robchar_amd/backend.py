@@ -702,6 +702,133 @@ def tail_select(fid, alpha: float, want=TAIL_SELECT_OUTPUTS, device=None):
     return res
 
 
+LBFGS_KINDS = {"raw": 0, "one_minus": 1, "one_minus_plus_std": 2}
+LBFGS_DEFAULTS = {"c1": 1e-4, "gtol": 1e-6, "ftol": 0.0, "maxiter": 100, "maxback": 20}
+
+
+def _lbfgs_dims(ndim: int, m: int):
+    ndim, m = int(ndim), int(m)
+    if not 3 <= ndim <= 13:
+        raise ValueError("ndim must be 3 .. 13 (N + 1, N = 2 .. max_nspin_grad())")
+    if not 1 <= m <= 8:
+        raise ValueError("m must be 1 .. 8")
+    return ndim, m
+
+
+def lbfgs_state_len(n_rows: int, ndim: int, m: int) -> int:
+    """Doubles of batched L-BFGS state for `n_rows` rows of `ndim` variables with `m` pairs (`rc_lbfgs_state_len`, host only)."""
+    ndim, m = _lbfgs_dims(ndim, m)
+    if int(n_rows) < 0:
+        raise ValueError("n_rows must be non-negative")
+    n = int(_lib.load().rc_lbfgs_state_len(int(n_rows), ndim, m))
+    if n < 0:
+        raise ValueError("rc_lbfgs_state_len: bad arguments")
+    return n
+
+
+def _lbfgs_tensor(t, shape, what):
+    import torch
+    if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        raise ValueError(f"{what}: a contiguous float64 CUDA tensor of shape {tuple(shape)}")
+    return t
+
+
+def lbfgs_init(x0, mask=None, m: int = 5):
+    """Start the batched L-BFGS state machine (`rc_lbfgs_init_f64_async`; the definition is `lbfgs.py`): x0 (C, n) float64 CUDA
+    tensor of start rows, `mask` (C, n) of 0 / 1 or None (a masked variable never moves) -> (state, trial): the opaque state
+    (fields, C) and the (C, n) trial points - the `controllers` of the next gradient launch.  Enqueued on the current stream."""
+    if not _is_torch(x0) or x0.ndim != 2:
+        raise ValueError("x0: a (C, n) float64 CUDA tensor")
+    C, n = (int(v) for v in x0.shape)
+    n, m = _lbfgs_dims(n, m)
+    import torch
+    x0 = _lbfgs_tensor(x0.contiguous() if x0.is_cuda and x0.dtype == torch.float64 else x0, (C, n), "x0")
+    if mask is not None:
+        mask = _lbfgs_tensor(mask, (C, n), "mask")
+        if mask.device != x0.device:
+            raise ValueError("mask lives on another device than x0")
+    lib = _lib.load()
+    _lib.require_gpu()
+    dev = x0.device
+    fields = 4 * n + 2 * m * n + m + 11
+    if lbfgs_state_len(C, n, m) != fields * C:
+        raise _lib.RobCharHipError("rc_lbfgs_state_len disagrees with the state layout of lbfgs.py")
+    state = torch.empty((fields, C), dtype=torch.float64, device=dev)
+    trial = torch.empty((C, n), dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.rc_lbfgs_init_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, ctypes.c_void_p(x0.data_ptr()),
+                                           ctypes.c_void_p(mask.data_ptr()) if mask is not None else None,
+                                           ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(trial.data_ptr())))
+    return state, trial
+
+
+def _lbfgs_state_dims(state, trial, m):
+    if not (_is_torch(trial) and trial.ndim == 2):
+        raise ValueError("trial: the (C, n) tensor of lbfgs_init")
+    C, n = (int(v) for v in trial.shape)
+    n, m = _lbfgs_dims(n, m)
+    _lbfgs_tensor(trial, (C, n), "trial")
+    _lbfgs_tensor(state, (4 * n + 2 * m * n + m + 11, C), "state")
+    if state.device != trial.device:
+        raise ValueError("state and trial live on different devices")
+    return C, n, m
+
+
+def lbfgs_advance(state, trial, row_a, row_b=None, *, m: int = 5, kind="one_minus", lam: float = 0.0, c1: float = 1e-4,
+                  gtol: float = 1e-6, ftol: float = 0.0, maxiter: int = 100, maxback: int = 20):
+    """One step of every row (`rc_lbfgs_advance_f64_async`): `row_a` (C, n + 1) holds what a gradient entry wrote for the rows
+    of `trial` - kind "raw": (f, g); "one_minus": a "mean" or "sum" row, f = 1 - a[0], g = -a[1:]; "one_minus_plus_std": `row_a`
+    = "mean", `row_b` = "moment", f = 1 - mean F + lam std F.  Per row: accept or backtrack, and the next trial point written
+    into `trial` in place (all NaN for a row that is done).  `m` as given to `lbfgs_init`.  Enqueue-only, current stream."""
+    if kind not in LBFGS_KINDS:
+        raise ValueError(f"kind: one of {tuple(LBFGS_KINDS)}")
+    C, n, m = _lbfgs_state_dims(state, trial, m)
+    _lbfgs_tensor(row_a, (C, n + 1), "row_a")
+    if kind == "one_minus_plus_std":
+        _lbfgs_tensor(row_b, (C, n + 1), "row_b")
+    else:
+        row_b = None
+    if not (0.0 < float(c1) < 1.0) or not float(gtol) >= 0.0 or not float(ftol) >= 0.0 or int(maxiter) < 1 or int(maxback) < 0:
+        raise ValueError("c1 in (0, 1), gtol >= 0, ftol >= 0, maxiter >= 1, maxback >= 0")
+    if any(t is not None and t.device != state.device for t in (row_a, row_b)):
+        raise ValueError("row_a / row_b live on another device than the state")
+    lib = _lib.load()
+    _lib.require_gpu()
+    import torch
+    dev = state.device
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.rc_lbfgs_advance_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, LBFGS_KINDS[kind], float(lam),
+                                              ctypes.c_void_p(row_a.data_ptr()),
+                                              ctypes.c_void_p(row_b.data_ptr()) if row_b is not None else None, float(c1), float(gtol),
+                                              float(ftol), int(maxiter), int(maxback), ctypes.c_void_p(state.data_ptr()),
+                                              ctypes.c_void_p(trial.data_ptr())))
+
+
+LBFGS_RESULT_OUTPUTS = ("x", "f", "grad", "status", "iters", "evals")
+
+
+def lbfgs_result(state, trial, *, m: int = 5, want=LBFGS_RESULT_OUTPUTS):
+    """The rows' results out of the state (`rc_lbfgs_result_f64_async`): dict of torch tensors on the state's device, the entries
+    named in `want`: "x" (C, n), "f" (C,), "grad" (C, n) float64, "status" (C,) int32 (0 running, 1 gtol, 2 ftol, 3 maxiter,
+    4 line search failed, 5 not finite), "iters" and "evals" (C,) int64.  Enqueue-only, current stream."""
+    want = tuple(want)
+    if not want or any(w not in LBFGS_RESULT_OUTPUTS for w in want):
+        raise ValueError(f"want: a non-empty subset of {LBFGS_RESULT_OUTPUTS}, got {want}")
+    C, n, m = _lbfgs_state_dims(state, trial, m)
+    lib = _lib.load()
+    _lib.require_gpu()
+    import torch
+    dev = state.device
+    shapes = {"x": ((C, n), torch.float64), "f": ((C,), torch.float64), "grad": ((C, n), torch.float64),
+              "status": ((C,), torch.int32), "iters": ((C,), torch.int64), "evals": ((C,), torch.int64)}
+    res = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
+    ptr = lambda k: ctypes.c_void_p(res[k].data_ptr()) if k in res else None
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.rc_lbfgs_result_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, ctypes.c_void_p(state.data_ptr()),
+                                             ptr("x"), ptr("f"), ptr("grad"), ptr("status"), ptr("iters"), ptr("evals")))
+    return res
+
+
 def mc_fidelity_directional(controllers, idx, ab, nspin: int, inspin: int, outspin: int, n_draws: int, h0_diag=None,
                             h0_offdiag=None, out=None):
     """Fidelities of `directional_perturbation` samples straight from (direction index, two normals) per sample

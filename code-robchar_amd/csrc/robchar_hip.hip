@@ -23,6 +23,7 @@
 //   reduce_kernel            one workgroup per controller: RIM_1, std, min, Q(thr) for the centre / DKW-upper /
 //                            DKW-lower variants in two passes over the K fidelities (fixed summation order).
 //   sort_*_kernel            row sort for the ECDF: merge sort in LDS (K <= 16384), chunked bitonic network above.
+//   lbfgs_advance_kernel     one LANE per controller row: the batched L-BFGS state machine (lbfgs_core.h), state [field][C]
 //   tail_select_kernel       one workgroup per row: list, CVaR weights and value at risk of the row's lower tail by a radix
 //                            select over an order-preserving key (no sort), compacted in index order.
 //   philox_normal_kernel     counter-based Gaussian draws for sample spaces too large to draw on the host.
@@ -50,6 +51,7 @@
 #include "csym_core.h"
 #include "sort_core.h"
 #include "select_core.h"
+#include "lbfgs_core.h"
 #include "legacy_rng_core.h"
 #include "mt19937_jump_poly.h"
 #include "ws_plan.h"
@@ -103,6 +105,7 @@ typedef __attribute__((address_space(3))) void* rc_lptr_t;
 #include "k_fidelity_dense.inc.h"
 #include "k_reduce_sort.inc.h"
 #include "k_tail_select.inc.h"
+#include "k_lbfgs.inc.h"
 #include "k_draws.inc.h"
 #include "k_fidelity_philox.inc.h"
 #include "k_directional.inc.h"
@@ -1786,6 +1789,83 @@ int rc_tail_select_f64_async(int device, void* stream, const double* fid_dev, lo
         hipLaunchKernelGGL((tail_select_kernel<512, kRedCache, true>), grid, dim3(512), 0, s, p);
     else
         hipLaunchKernelGGL((tail_select_kernel<512, kSelLongU, false>), grid, dim3(512), 0, s, p);
+    RC_HIP_CHECK(hipGetLastError());
+    return RC_OK;
+}
+
+// ---- batched L-BFGS (ABI 13): the state machine of lbfgs.py, one lane per row (k_lbfgs.inc.h) ----------------------------------
+static int check_lbfgs(int ndim, int m, long long C) {
+    if (ndim < rclb::kMinDim || ndim > rclb::kMaxDim) return fail(RC_EINVAL, "ndim must be 3 .. 13 (N + 1, N = 2 .. RC_MAX_NSPIN_GRAD)");
+    if (m < 1 || m > rclb::kMaxM) return fail(RC_EINVAL, "m must be 1 .. 8");
+    if (C < 0) return fail(RC_EINVAL, "C must be non-negative");
+    if (C > 0x7fffffffLL) return fail(RC_EINVAL, "too many rows for one launch");
+    return RC_OK;
+}
+
+long long rc_lbfgs_state_len(long long C, int ndim, int m) {
+    if (check_lbfgs(ndim, m, C)) return -1;
+    return C * (long long)rclb::Layout{ndim, m}.fields();
+}
+
+int rc_lbfgs_init_f64_async(int device, void* stream, int ndim, int m, long long C, const double* x0_dev, const double* mask_dev,
+                            double* state_dev, double* trial_dev) {
+    if (int rc = check_lbfgs(ndim, m, C)) return rc;
+    if (C == 0) return RC_OK;
+    if (!state_dev) return fail(RC_EINVAL, "NULL array pointer (state)");
+    if (!x0_dev || !trial_dev) return fail(RC_EINVAL, "NULL array pointer (x0, trial)");
+    RC_HIP_CHECK(hipSetDevice(device));
+    hipLaunchKernelGGL(lbfgs_init_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, (hipStream_t)stream, state_dev, trial_dev, x0_dev,
+                       mask_dev, C, ndim, m);
+    RC_HIP_CHECK(hipGetLastError());
+    return RC_OK;
+}
+
+int rc_lbfgs_advance_f64_async(int device, void* stream, int ndim, int m, long long C, int kind, double lam, const double* row_a_dev,
+                               const double* row_b_dev, double c1, double gtol, double ftol, long long maxiter, long long maxback,
+                               double* state_dev, double* trial_dev) {
+    if (int rc = check_lbfgs(ndim, m, C)) return rc;
+    if (kind < rclb::kRaw || kind > rclb::kOneMinusPlusStd) return fail(RC_EINVAL, "kind must be 0 (raw), 1 (one_minus) or 2 (one_minus_plus_std)");
+    if (!(c1 > 0.0 && c1 < 1.0)) return fail(RC_EINVAL, "c1 must be in (0, 1)");
+    if (!(gtol >= 0.0) || !(ftol >= 0.0)) return fail(RC_EINVAL, "gtol and ftol must be non-negative");
+    if (maxiter < 1 || maxback < 0) return fail(RC_EINVAL, "maxiter must be positive and maxback non-negative");
+    if (C == 0) return RC_OK;
+    if (!state_dev) return fail(RC_EINVAL, "NULL array pointer (state)");
+    if (!row_a_dev || !trial_dev) return fail(RC_EINVAL, "NULL array pointer (row_a, trial)");
+    if (kind == rclb::kOneMinusPlusStd && !row_b_dev) return fail(RC_EINVAL, "NULL array pointer (row_b: kind 2 reads the moment rows)");
+    RC_HIP_CHECK(hipSetDevice(device));
+    LbfgsAdvanceParams p{};
+    p.state = state_dev;
+    p.trial = trial_dev;
+    p.a = row_a_dev;
+    p.b = row_b_dev;
+    p.C = C;
+    p.m = m;
+    p.kind = kind;
+    p.lam = lam;
+    p.opt = rclb::Params{c1, gtol, ftol, maxiter, maxback};
+    const dim3 grid((unsigned)((C + 63) / 64));
+    hipStream_t s = (hipStream_t)stream;
+    switch (ndim) {
+#define RC_CASE(n) \
+    case n: hipLaunchKernelGGL(lbfgs_advance_kernel<n>, grid, dim3(64), 0, s, p); break;
+        RC_CASE(3) RC_CASE(4) RC_CASE(5) RC_CASE(6) RC_CASE(7) RC_CASE(8) RC_CASE(9) RC_CASE(10) RC_CASE(11) RC_CASE(12) RC_CASE(13)
+#undef RC_CASE
+    }
+    RC_HIP_CHECK(hipGetLastError());
+    return RC_OK;
+}
+
+int rc_lbfgs_result_f64_async(int device, void* stream, int ndim, int m, long long C, const double* state_dev, double* x_out_dev,
+                              double* f_out_dev, double* g_out_dev, int* status_out_dev, long long* iters_out_dev,
+                              long long* evals_out_dev) {
+    if (int rc = check_lbfgs(ndim, m, C)) return rc;
+    if (!x_out_dev && !f_out_dev && !g_out_dev && !status_out_dev && !iters_out_dev && !evals_out_dev)
+        return fail(RC_EINVAL, "no output requested (x_out, f_out, g_out, status_out, iters_out and evals_out are all NULL)");
+    if (C == 0) return RC_OK;
+    if (!state_dev) return fail(RC_EINVAL, "NULL array pointer (state)");
+    RC_HIP_CHECK(hipSetDevice(device));
+    hipLaunchKernelGGL(lbfgs_result_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, (hipStream_t)stream, state_dev, C, ndim, m,
+                       x_out_dev, f_out_dev, g_out_dev, status_out_dev, iters_out_dev, evals_out_dev);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
 }

@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from . import backend
+from . import backend, lbfgs
 
 
 class noise_function:
@@ -387,6 +387,33 @@ class noise_model_base:
         mean, moment = (v.cpu().numpy() if backend._is_torch(v) else np.asarray(v) for v in (res["mean"], res["moment"]))
         return {k: v.copy() for k, v in moments_from_sums(mean, moment).items()}
 
+    def _cvar_device(self, ctrl, K: int, seed: int, alpha: float, sigma, offset: int, shared: bool, diag, off):
+        """The device-resident part of `fidelity_cvar_philox`: ctrl (C, N+1) float64 CUDA tensor, `sigma` a float or a (C,) tensor
+        on its device -> (sum (C, N+2) = (CVaR, d CVaR / dx), var (C,)) as tensors on the current stream, nothing synchronised:
+        the fidelity launch, the tail selection and the listed-sample gradient launch."""
+        import torch
+        N = self.Nspin
+        rows = np.ndim(sigma) > 0
+        if not shared:
+            fid = backend.mc_fidelity_philox(ctrl, K, N, self.inspin, self.outspin, seed, offset=offset, sigma=sigma, h0_diag=diag,
+                                             h0_offdiag=off)
+        elif not rows:
+            with torch.cuda.device(ctrl.device):
+                draws = backend.philox_normal((1, K, N, 3), seed, scale=float(sigma), offset=offset, as_torch=True)
+            fid = backend.mc_fidelity(ctrl, draws, N, self.inspin, self.outspin, h0_diag=diag, h0_offdiag=off)
+        else:                                      # (one draw set, one scale per row: no fidelity-only kernel takes that)
+            fid = backend.mc_fidelity_grad_philox(ctrl, K, N, self.inspin, self.outspin, seed, offset=offset, sigma=sigma, shared=True,
+                                                  h0_diag=diag, h0_offdiag=off, want=("fid",))["fid"]
+        if _tail_select_routed(K):                 # list, weights and value at risk from ONE selection launch
+            sel = backend.tail_select(fid, alpha)
+            listed, weights, var = sel["list"], sel["weight"], sel["var"]
+        else:
+            listed, weights = _tail_weights_torch(fid, alpha)
+            var = torch.gather(fid, 1, listed.clamp(min=0).long()).max(dim=1).values   # (a NaN row gathers NaN)
+        res = backend.mc_fidelity_grad_listed(ctrl, K, listed, weights, nspin=N, inspin=self.inspin, outspin=self.outspin, seed=seed,
+                                              offset=offset, sigma=sigma, shared=shared, h0_diag=diag, h0_offdiag=off, want=("sum",))
+        return res["sum"], var
+
     def fidelity_cvar_philox(self, controllers, n_draws: int, seed: int, alpha: float, sigma=None, offset: int = 0,
                              shared: bool = False):
         """CVaR_alpha of the fidelity - the mean of the worst alpha K of `n_draws` counter-based draws per controller - with its
@@ -412,36 +439,92 @@ class noise_model_base:
         if not backend._is_torch(controllers):
             controllers = np.asarray(controllers, dtype=np.float64).reshape(-1, self.Nspin + 1)
         import torch
-        N, K = self.Nspin, int(n_draws)
         ctrl = (controllers if backend._is_torch(controllers) else torch.from_numpy(controllers).to(backend.compute_device()))
         ctrl = ctrl.to(dtype=torch.float64).contiguous()
-        rows = np.ndim(sigma) > 0
-        if rows:
+        if np.ndim(sigma) > 0:
             sigma = (sigma if backend._is_torch(sigma) else torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)))
             sigma = sigma.to(device=ctrl.device, dtype=torch.float64)
-        if not shared:
-            fid = backend.mc_fidelity_philox(ctrl, K, N, self.inspin, self.outspin, seed, offset=offset, sigma=sigma, h0_diag=diag,
-                                             h0_offdiag=off)
-        elif not rows:
-            with torch.cuda.device(ctrl.device):
-                draws = backend.philox_normal((1, K, N, 3), seed, scale=float(sigma), offset=offset, as_torch=True)
-            fid = backend.mc_fidelity(ctrl, draws, N, self.inspin, self.outspin, h0_diag=diag, h0_offdiag=off)
-        else:                                      # (one draw set, one scale per row: no fidelity-only kernel takes that)
-            fid = backend.mc_fidelity_grad_philox(ctrl, K, N, self.inspin, self.outspin, seed, offset=offset, sigma=sigma, shared=True,
-                                                  h0_diag=diag, h0_offdiag=off, want=("fid",))["fid"]
-        if _tail_select_routed(K):                 # list, weights and value at risk from ONE selection launch
-            sel = backend.tail_select(fid, alpha)
-            listed, weights, var = sel["list"], sel["weight"], sel["var"]
-        else:
-            listed, weights = _tail_weights_torch(fid, alpha)
-            var = torch.gather(fid, 1, listed.clamp(min=0).long()).max(dim=1).values   # (a NaN row gathers NaN)
-        res = backend.mc_fidelity_grad_listed(ctrl, K, listed, weights, nspin=N, inspin=self.inspin, outspin=self.outspin, seed=seed,
-                                              offset=offset, sigma=sigma, shared=shared, h0_diag=diag, h0_offdiag=off, want=("sum",))
-        total = res["sum"].cpu().numpy()
+        total, var = self._cvar_device(ctrl, int(n_draws), seed, alpha, sigma, offset, shared, diag, off)
+        total = total.cpu().numpy()
         nan = np.isnan(ctrl.cpu().numpy()).any(axis=1)
         var = var.cpu().numpy().copy()
         var[nan] = np.nan
         return {"cvar": total[:, 0].copy(), "grad_cvar": total[:, 1:].copy(), "var": var}
+
+    def optimize_controllers(self, controllers, n_draws: int, seed: int, objective="mean", sigma=None, offset: int = 0,
+                             shared: bool = True, mask=None, max_evals: int = 60, poll: int = 8, **lbfgs_params):
+        """Robust re-optimisation of ALL controller rows at once by the batched L-BFGS state machine on the device
+        (`backend.lbfgs_init` / `lbfgs_advance`; the definition is `lbfgs.py`): per evaluation ONE gradient launch over the rows'
+        trial points and one advance launch, everything device-resident on the current stream.  Objective, over `n_draws`
+        counter-based draws per row generated inside the kernels:
+
+            "mean"             1 - mean F                        `mc_fidelity_grad_philox`, want = ("mean",)
+            ("std", lam)       1 - mean F + lam std F            ... want = ("mean", "moment")
+            ("cvar", alpha)    1 - CVaR_alpha F                  the three launches of `fidelity_cvar_philox`
+
+        shared=True (common random numbers, the default): every row and every evaluation sees the same draws, so the objective is
+        a deterministic function of the controller - what a line search needs.  `mask` (C, N+1) of 0 / 1 or None: a masked entry
+        never moves (mask[:, N] = 0 fixes the time T); there are no bounds on the variables.  `lbfgs_params`: m (5), c1 (1e-4),
+        gtol (1e-6), ftol (0 = off), maxiter (100), maxback (20).  At most `max_evals` evaluations; every `poll` evaluations the
+        status column is copied to the host and the loop stops when no row is running - the only synchronisation.
+        Returns NumPy arrays {"x" (C, N+1), "f" (C,), "grad" (C, N+1), "status" (C,), "iters" (C,), "evals" (C,)}: the best
+        accepted point of every row, its objective value and gradient; status 0 = still running after `max_evals`, 1 gtol, 2
+        ftol, 3 maxiter, 4 line search failed, 5 not finite / NaN row.  Chain topology with real static couplings, N <= 12, one
+        GPU."""
+        diag, off, ring, imag = self._static_terms()
+        if ring:
+            raise NotImplementedError("the fidelity gradient is implemented for the chain topology only")
+        if imag.any():
+            raise NotImplementedError("draws generated inside the gradient kernel: real static couplings only")
+        if objective == "mean":
+            kind, par = "one_minus", 0.0
+        elif isinstance(objective, (tuple, list)) and len(objective) == 2 and objective[0] in ("std", "cvar"):
+            kind, par = ("one_minus_plus_std" if objective[0] == "std" else "cvar"), float(objective[1])
+            if kind == "cvar" and not (0.0 < par <= 1.0):
+                raise ValueError("alpha must be in (0, 1]")
+        else:
+            raise ValueError('objective: "mean", ("std", lam) or ("cvar", alpha)')
+        K, N = int(n_draws), self.Nspin
+        if K < 1 or int(max_evals) < 1 or int(poll) < 1:
+            raise ValueError("n_draws, max_evals and poll must be positive")
+        m = int(lbfgs_params.pop("m", 5))
+        unknown = set(lbfgs_params) - set(backend.LBFGS_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown L-BFGS parameters {sorted(unknown)}")
+        if sigma is None:
+            sigma = float(self.rng.args.get("scale", self.noise))
+        import torch
+        if not backend._is_torch(controllers):
+            controllers = torch.from_numpy(np.asarray(controllers, dtype=np.float64).reshape(-1, N + 1)).to(backend.compute_device())
+        x0 = controllers.to(dtype=torch.float64).contiguous()
+        if tuple(x0.shape[1:]) != (N + 1,):
+            raise ValueError(f"controllers: expected (C, {N + 1})")
+        dev = x0.device
+        if np.ndim(sigma) > 0:
+            sigma = (sigma if backend._is_torch(sigma) else torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64)))
+            sigma = sigma.to(device=dev, dtype=torch.float64)
+        if mask is not None:
+            mask = (mask if backend._is_torch(mask) else torch.from_numpy(np.array(np.broadcast_to(np.asarray(mask, dtype=np.float64),
+                                                                                                 tuple(x0.shape)))))
+            mask = mask.to(device=dev, dtype=torch.float64).contiguous()
+        geo = dict(h0_diag=diag, h0_offdiag=off)
+        state, trial = backend.lbfgs_init(x0, mask, m=m)
+        status = state[lbfgs.field_offsets(N + 1, m)["status"]]
+        for ev in range(1, int(max_evals) + 1):
+            row_b = None
+            if kind == "cvar":
+                row_a, _ = self._cvar_device(trial, K, seed, par, sigma, offset, shared, diag, off)
+            else:
+                want = ("mean", "moment") if kind == "one_minus_plus_std" else ("mean",)
+                res = backend.mc_fidelity_grad_philox(trial, K, N, self.inspin, self.outspin, seed, offset=offset, sigma=sigma,
+                                                      shared=shared, want=want, **geo)
+                row_a, row_b = res["mean"], res.get("moment")
+            backend.lbfgs_advance(state, trial, row_a, row_b, m=m, kind="one_minus" if kind == "cvar" else kind, lam=par,
+                                  **lbfgs_params)
+            if ev % int(poll) == 0 and ev < int(max_evals) and not bool((status == 0.0).any().item()):
+                break
+        res = backend.lbfgs_result(state, trial, m=m)
+        return {k: v.cpu().numpy() for k, v in res.items()}
 
     def nominal_sensitivity(self, controllers):
         """(C, N, 3): dF/d(perturbation) of the unperturbed system per structured direction - the differential sensitivity at

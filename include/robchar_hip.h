@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 12      /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 13      /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -63,7 +63,9 @@ extern "C" {
                                   9: + rc_mc_fidelity_sens_philox_f64_async (additive);
                                   10: + rc_mc_fidelity_grad_philox_f64_async (additive);
                                   11: + rc_mc_fidelity_grad_listed_f64_async (additive);
-                                  12: + rc_tail_select_len, rc_tail_select_f64_async (additive) */
+                                  12: + rc_tail_select_len, rc_tail_select_f64_async (additive);
+                                  13: + rc_lbfgs_state_len, rc_lbfgs_init_f64_async, rc_lbfgs_advance_f64_async,
+                                      rc_lbfgs_result_f64_async (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -338,6 +340,49 @@ int rc_mc_fidelity_grad_listed_f64_async(int device, void* stream, int N, int in
 long long rc_tail_select_len(long long K, double alpha);
 int rc_tail_select_f64_async(int device, void* stream, const double* fid_dev, long long C, long long K, double alpha,
                              int* list_out_dev, double* weight_out_dev, double* var_out_dev);
+
+/* (ABI 13) Batched L-BFGS with a backtracking line search, one independent problem per controller row, as a state machine on
+ * the device: the optimiser that consumes the C rows of value and gradient the gradient entries above write per launch.  The loop
+ * of a client is   init;  repeat { gradient launch on trial_dev -> advance }  - enqueue-only on one stream, rows in different
+ * phases (first value, accepted step, backtracking, done) in the same launch.  The definition is code-robchar_amd/lbfgs.py (NumPy):
+ * every dot product accumulated sequentially over the variable index, every product rounded once, IEEE division and square root;
+ * the kernels give its bits (a NaN's sign and payload excepted).
+ *     ndim      variables per row, 3 .. 13: the controller row of N = 2 .. RC_MAX_NSPIN_GRAD spins (N biases, then T)
+ *     m         pairs kept per row, 1 .. 8
+ *     state_dev rc_lbfgs_state_len(C, ndim, m) = C (4 ndim + 2 m ndim + m + 11) doubles, caller-owned, laid out [field][C]; opaque
+ *               to a client (lbfgs.field_offsets names the fields); rc_lbfgs_state_len is host only, -1 on bad arguments
+ *     trial_dev [C][ndim]: the `controllers_dev` argument of the next gradient launch.  The row of a DONE row is all NaN, which the
+ *               gradient entries skip (their NaN-row rule); a done row's state never changes again.
+ * rc_lbfgs_init_f64_async: x0_dev [C][ndim] start rows; mask_dev [C][ndim] of 0.0 / 1.0 or NULL (= all free): the gradient is
+ *     multiplied by it, so a masked variable never moves (fix T this way).  Bounds on the variables are not supported.  A start row
+ *     with a NaN is done at once (status 5).
+ * rc_lbfgs_advance_f64_async: one (value, gradient) per row, evaluated at trial_dev, from row_a_dev [C][ndim + 1]:
+ *     kind 0  raw                  (f, g_0 .. g_{ndim-1}) as they are
+ *     kind 1  one_minus            row_a = a `mean_out` row of the gradient entries or a `sum_out` row of the listed entry:
+ *                                  f = 1 - a[0], g = -a[1 ..]
+ *     kind 2  one_minus_plus_std   row_a = mean_out, row_b_dev [C][ndim + 1] = moment_out of rc_mc_fidelity_grad_philox_f64_async:
+ *                                  f = (1 - mean F) + lam std F and its gradient, std by the arithmetic and the floor rule of
+ *                                  noise.moments_from_sums.  row_b_dev and lam are read by kind 2 only.
+ *     A trial point is accepted when its value is finite and f_trial <= f + (c1 t) g.d (Armijo); otherwise the step is halved; after
+ *     more than `maxback` halvings the history is dropped once (steepest descent, first step min(1, 1 / |g|_2)), then the row ends.
+ *     c1 in (0, 1); gtol on max |g_i|; ftol = 0 switches the value test off; maxiter >= 1 accepted steps.
+ *     status: 0 running, 1 max |g_i| <= gtol, 2 fprev - f <= ftol max(|fprev|, |f|, 1), 3 maxiter reached, 4 line search failed,
+ *     5 first value or gradient not finite, or a NaN start row.
+ * rc_lbfgs_result_f64_async: the rows' results out of the state: x_out [C][ndim], f_out [C], g_out [C][ndim], status_out [C] int32,
+ *     iters_out [C] and evals_out [C] int64 (accepted steps, evaluations consumed); each optional, RC_EINVAL "no output" when all
+ *     are NULL.
+ * Argument checks before any HIP call: ndim outside 3 .. 13, m outside 1 .. 8, C negative, a bad kind or parameter: RC_EINVAL;
+ * C = 0: RC_OK, nothing done; state_dev (or another required pointer) NULL: RC_EINVAL.  Enqueue-only: device pointers, launched on
+ * `stream`, no allocation, no synchronisation.  One lane per row, no atomics: same inputs, same bits. */
+long long rc_lbfgs_state_len(long long C, int ndim, int m);
+int rc_lbfgs_init_f64_async(int device, void* stream, int ndim, int m, long long C, const double* x0_dev, const double* mask_dev,
+                            double* state_dev, double* trial_dev);
+int rc_lbfgs_advance_f64_async(int device, void* stream, int ndim, int m, long long C, int kind, double lam,
+                               const double* row_a_dev, const double* row_b_dev, double c1, double gtol, double ftol,
+                               long long maxiter, long long maxback, double* state_dev, double* trial_dev);
+int rc_lbfgs_result_f64_async(int device, void* stream, int ndim, int m, long long C, const double* state_dev, double* x_out_dev,
+                              double* f_out_dev, double* g_out_dev, int* status_out_dev, long long* iters_out_dev,
+                              long long* evals_out_dev);
 
 /* (ABI 6) 1 when the kernel above is the faster of the two bit-identical routes for this geometry (N <= 13, or N = 14 with
  * {in, out} = {0, N-1}), else 0; 0 everywhere when ROBCHAR_PHILOX_FUSED=0 is in the environment (read per call).  The ONE

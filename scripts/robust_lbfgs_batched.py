@@ -1,0 +1,64 @@
+#!/usr/bin/env python
+"""Robust re-optimisation of the shipped N = 7 controllers ALL AT ONCE on the GPU: the batched L-BFGS state machine on the device
+(`noise_model_base.optimize_controllers`) - one gradient launch over all rows and one advance launch per evaluation, nothing
+but the status column ever returns to the host.  scripts/robust_lbfgs.py does one row through SciPy.
+
+    python scripts/robust_lbfgs_batched.py [--rows 57] [--sigma 0.05] [--evals 60] [--train 1000] [--pair 0-6] [--risk LAM | --cvar ALPHA]
+
+The objective is 1 - mean F (--risk LAM: + LAM std F; --cvar ALPHA: 1 - CVaR_ALPHA F) over `train` shared counter-based draws
+(common random numbers); the test figure of a row is 1 - mean F over 10 000 draws of the same stream behind the training draws.
+Prints start / final / test value per row; `run()` returns them for callers (tests)."""
+import argparse
+import importlib
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+
+def run(rows=None, sigma=0.05, evals=60, train=1000, pair="0-6", verbose=True, risk=0.0, cvar=None, seed=0x5EED0010, **lbfgs_params):
+    if cvar is not None and risk != 0.0:
+        raise ValueError("cvar and risk are two objectives: give one of them")
+    noise = importlib.import_module("code-robchar_amd.noise")
+    z = np.load(os.path.join(ROOT, "tests", "golden", "lbfgs_n7.npz"))
+    x0 = np.array(z["ctrl_" + pair], dtype=np.float64)
+    x0 = x0[: x0.shape[0] if rows is None else int(rows)]
+    a, b = (int(v) for v in pair.split("-"))
+    nm = noise.structured_perturbation(Nspin=7, inspin=a, outspin=b, noise=sigma)
+    objective = ("cvar", cvar) if cvar is not None else ("std", risk) if risk != 0.0 else "mean"
+
+    def value(x, n_draws, offset):
+        if cvar is not None:
+            return 1.0 - nm.fidelity_cvar_philox(x, n_draws, seed, cvar, sigma=sigma, offset=offset, shared=True)["cvar"]
+        mo = nm.fidelity_moments_philox(x, n_draws, seed, sigma=sigma, offset=offset, shared=True)
+        return 1.0 - mo["fav"] + risk * mo["std"]
+    start = value(x0, train, 0)
+    res = nm.optimize_controllers(x0, train, seed, objective=objective, sigma=sigma, shared=True, max_evals=evals, **lbfgs_params)
+    test_start, test_final = (1.0 - nm.fidelity_moments_philox(x, 10000, seed, sigma=sigma, offset=train * 7 * 3, shared=True)["fav"]
+                              for x in (x0, res["x"]))
+    if verbose:
+        print(f"# objective {objective}, sigma = {sigma}, {train} shared draws, at most {evals} evaluations; test: 1 - mean F over 10 000 draws")
+        print("# row      start        final   test start   test final  status iters evals")
+        for c in range(x0.shape[0]):
+            print(f"{c:5d} {start[c]:12.8f} {res['f'][c]:12.8f} {test_start[c]:12.8f} {test_final[c]:12.8f} {res['status'][c]:7d} "
+                  f"{res['iters'][c]:5d} {res['evals'][c]:5d}")
+        print(f"# mean   {start.mean():12.8f} {res['f'].mean():12.8f} {test_start.mean():12.8f} {test_final.mean():12.8f}")
+    return {"x0": x0, "start": start, "test_start": test_start, "test_final": test_final, "model": nm, "objective": objective, **res}
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--rows", type=int, default=None)
+    ap.add_argument("--sigma", type=float, default=0.05)
+    ap.add_argument("--evals", type=int, default=60)
+    ap.add_argument("--train", type=int, default=1000)
+    ap.add_argument("--pair", default="0-6", choices=("0-6", "0-3"))
+    goal = ap.add_mutually_exclusive_group()
+    goal.add_argument("--risk", type=float, default=0.0)
+    goal.add_argument("--cvar", type=float, default=None, metavar="ALPHA")
+    args = ap.parse_args()
+    run(args.rows, args.sigma, args.evals, args.train, args.pair, risk=args.risk, cvar=args.cvar)
