@@ -30,6 +30,7 @@ EXPORTS = (
     "rc_mc_fidelity_sens_philox_f64_async", "rc_mc_fidelity_grad_philox_f64_async",
     "rc_mc_fidelity_grad_listed_f64_async", "rc_tail_select_len", "rc_tail_select_f64_async",
     "rc_lbfgs_state_len", "rc_lbfgs_init_f64_async", "rc_lbfgs_advance_f64_async", "rc_lbfgs_result_f64_async",
+    "rc_lbfgs_init_box_f64_async", "rc_lbfgs_advance_box_f64_async",
 )
 
 RC_KERNEL_AUTO, RC_KERNEL_TRIDIAG_QL, RC_KERNEL_JACOBI, RC_KERNEL_TRIDIAG_ADJ, RC_KERNEL_EXPM, RC_KERNEL_RING_HH = 0, 1, 2, 3, 4, 5
@@ -169,6 +170,8 @@ def load():
     lib.rc_lbfgs_init_f64_async.argtypes = [i, vp, i, i, ll, dp, dp, dp, dp]
     lib.rc_lbfgs_advance_f64_async.argtypes = [i, vp, i, i, ll, i, dbl, dp, dp, dbl, dbl, dbl, ll, ll, dp, dp]
     lib.rc_lbfgs_result_f64_async.argtypes = [i, vp, i, i, ll, dp, dp, dp, dp, vp, vp, vp]
+    lib.rc_lbfgs_init_box_f64_async.argtypes = [i, vp, i, i, ll, dp, dp, dp, dp, dp, dp]
+    lib.rc_lbfgs_advance_box_f64_async.argtypes = [i, vp, i, i, ll, i, dbl, dp, dp, dp, dp, dbl, dbl, dbl, ll, ll, dp, dp]
     _lib = lib
     return lib
 

@@ -733,10 +733,31 @@ def _lbfgs_tensor(t, shape, what):
     return t
 
 
-def lbfgs_init(x0, mask=None, m: int = 5):
+def _lbfgs_bounds(bounds, like):
+    """bounds = (lo, hi), tensors broadcastable to the (C, n) of `like` -> two contiguous float64 (C, n) tensors on its device (a
+    tensor that already is one is passed through, so a caller who expands once hands in the same storage at every call)"""
+    import torch
+    if not (isinstance(bounds, (tuple, list)) and len(bounds) == 2 and all(_is_torch(b) for b in bounds)):
+        raise ValueError("bounds: a pair (lo, hi) of torch tensors broadcastable to (C, n)")
+    out = []
+    for b, what in zip(bounds, ("lo", "hi")):
+        if b.device != like.device:
+            raise ValueError(f"bounds: {what} lives on another device than the rows")
+        try:
+            b = b.to(dtype=torch.float64).expand(tuple(like.shape)).contiguous()
+        except RuntimeError:
+            raise ValueError(f"bounds: {what} of shape {tuple(b.shape)} does not broadcast to {tuple(like.shape)}") from None
+        out.append(b)
+    return out
+
+
+def lbfgs_init(x0, mask=None, m: int = 5, bounds=None):
     """Start the batched L-BFGS state machine (`rc_lbfgs_init_f64_async`; the definition is `lbfgs.py`): x0 (C, n) float64 CUDA
     tensor of start rows, `mask` (C, n) of 0 / 1 or None (a masked variable never moves) -> (state, trial): the opaque state
-    (fields, C) and the (C, n) trial points - the `controllers` of the next gradient launch.  Enqueued on the current stream."""
+    (fields, C) and the (C, n) trial points - the `controllers` of the next gradient launch.  Enqueued on the current stream.
+    `bounds` = (lo, hi), tensors broadcastable to (C, n) with -inf / +inf for a side without a bound: the BOXED machine
+    (`rc_lbfgs_init_box_f64_async`) - the start rows are projected into the box, and every `lbfgs_advance` of this state must be
+    given the same bounds."""
     if not _is_torch(x0) or x0.ndim != 2:
         raise ValueError("x0: a (C, n) float64 CUDA tensor")
     C, n = (int(v) for v in x0.shape)
@@ -747,6 +768,8 @@ def lbfgs_init(x0, mask=None, m: int = 5):
         mask = _lbfgs_tensor(mask, (C, n), "mask")
         if mask.device != x0.device:
             raise ValueError("mask lives on another device than x0")
+    if bounds is not None:
+        lo, hi = _lbfgs_bounds(bounds, x0)
     lib = _lib.load()
     _lib.require_gpu()
     dev = x0.device
@@ -756,6 +779,12 @@ def lbfgs_init(x0, mask=None, m: int = 5):
     state = torch.empty((fields, C), dtype=torch.float64, device=dev)
     trial = torch.empty((C, n), dtype=torch.float64, device=dev)
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if bounds is not None:
+        _lib.check(lib.rc_lbfgs_init_box_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, ctypes.c_void_p(x0.data_ptr()),
+                                                   ctypes.c_void_p(mask.data_ptr()) if mask is not None else None,
+                                                   ctypes.c_void_p(lo.data_ptr()), ctypes.c_void_p(hi.data_ptr()),
+                                                   ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(trial.data_ptr())))
+        return state, trial
     _lib.check(lib.rc_lbfgs_init_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, ctypes.c_void_p(x0.data_ptr()),
                                            ctypes.c_void_p(mask.data_ptr()) if mask is not None else None,
                                            ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(trial.data_ptr())))
@@ -775,8 +804,9 @@ def _lbfgs_state_dims(state, trial, m):
 
 
 def lbfgs_advance(state, trial, row_a, row_b=None, *, m: int = 5, kind="one_minus", lam: float = 0.0, c1: float = 1e-4,
-                  gtol: float = 1e-6, ftol: float = 0.0, maxiter: int = 100, maxback: int = 20):
-    """One step of every row (`rc_lbfgs_advance_f64_async`): `row_a` (C, n + 1) holds what a gradient entry wrote for the rows
+                  gtol: float = 1e-6, ftol: float = 0.0, maxiter: int = 100, maxback: int = 20, bounds=None):
+    """One step of every row (`rc_lbfgs_advance_f64_async`; with `bounds` = the (lo, hi) given to `lbfgs_init`, the boxed
+    `rc_lbfgs_advance_box_f64_async`: projected trial points, the active set, the projected-gradient test): `row_a` (C, n + 1) holds what a gradient entry wrote for the rows
     of `trial` - kind "raw": (f, g); "one_minus": a "mean" or "sum" row, f = 1 - a[0], g = -a[1:]; "one_minus_plus_std": `row_a`
     = "mean", `row_b` = "moment", f = 1 - mean F + lam std F.  Per row: accept or backtrack, and the next trial point written
     into `trial` in place (all NaN for a row that is done).  `m` as given to `lbfgs_init`.  Enqueue-only, current stream."""
@@ -792,11 +822,21 @@ def lbfgs_advance(state, trial, row_a, row_b=None, *, m: int = 5, kind="one_minu
         raise ValueError("c1 in (0, 1), gtol >= 0, ftol >= 0, maxiter >= 1, maxback >= 0")
     if any(t is not None and t.device != state.device for t in (row_a, row_b)):
         raise ValueError("row_a / row_b live on another device than the state")
+    if bounds is not None:
+        lo, hi = _lbfgs_bounds(bounds, trial)
     lib = _lib.load()
     _lib.require_gpu()
     import torch
     dev = state.device
     stream = torch.cuda.current_stream(dev).cuda_stream
+    if bounds is not None:
+        _lib.check(lib.rc_lbfgs_advance_box_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, LBFGS_KINDS[kind], float(lam),
+                                                      ctypes.c_void_p(row_a.data_ptr()),
+                                                      ctypes.c_void_p(row_b.data_ptr()) if row_b is not None else None,
+                                                      ctypes.c_void_p(lo.data_ptr()), ctypes.c_void_p(hi.data_ptr()), float(c1),
+                                                      float(gtol), float(ftol), int(maxiter), int(maxback),
+                                                      ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(trial.data_ptr())))
+        return
     _lib.check(lib.rc_lbfgs_advance_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, LBFGS_KINDS[kind], float(lam),
                                               ctypes.c_void_p(row_a.data_ptr()),
                                               ctypes.c_void_p(row_b.data_ptr()) if row_b is not None else None, float(c1), float(gtol),

@@ -8,6 +8,11 @@
 // consecutive rows, so every access is 64 consecutive doubles.  Integers (count, head, nback, iters, evals, status, first) are
 // stored as doubles.  The step is written against a row accessor (ld / st on a field, trial_ld / trial_st on the row of the
 // (C, n) trial array); StridedRow is the one the kernels and the host test use.
+//
+// Two variants of the machine share this text: the unbounded one (advance_row, init_row) and the BOXED one (advance_row_box,
+// init_row_box: box bounds lo <= x <= hi, projected steps - the rules are in lbfgs.py).  The step is advance_row_t<NDIM, BOX>;
+// everything boxed sits behind `if constexpr (BOX)`, so the unbounded instantiation is the code it was before the box existed.
+// The bounds are not state: lo and hi are the row's [n] bounds, handed in at every call.
 #pragma once
 
 #ifndef RC_HD
@@ -151,18 +156,26 @@ RCLB_UNROLL
     }
 }
 
+// P(v): a NaN stays a NaN
+RC_HD double clip(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// lo == nullptr: the unbounded machine; otherwise the boxed one (lo and hi both given): x0 is projected, bad bounds end the row
 template <class Row>
-RC_HD void init_row(const Row& r, const Layout& L, const double* x0, const double* mask) {
+RC_HD void init_row_t(const Row& r, const Layout& L, const double* x0, const double* mask, const double* lo, const double* hi) {
     bool bad = false;
     for (int i = 0; i < L.n; ++i) {
-        const double v = x0[i];
+        double v = x0[i];
         bad |= v != v;
+        if (lo) {
+            bad |= lo[i] != lo[i] || hi[i] != hi[i] || lo[i] > hi[i];
+            v = clip(v, lo[i], hi[i]);
+        }
         r.st(L.x() + i, v);
         r.st(L.g() + i, quiet_nan());
         r.st(L.d() + i, 0.0);
         r.st(L.mask() + i, mask ? mask[i] : 1.0);
     }
-    for (int i = 0; i < L.n; ++i) r.trial_st(i, bad ? quiet_nan() : x0[i]);
+    for (int i = 0; i < L.n; ++i) r.trial_st(i, bad ? quiet_nan() : (lo ? clip(x0[i], lo[i], hi[i]) : x0[i]));
     for (int k = 0; k < L.m * L.n; ++k) {
         r.st(L.S() + k, 0.0);
         r.st(L.Y() + k, 0.0);
@@ -181,6 +194,16 @@ RC_HD void init_row(const Row& r, const Layout& L, const double* x0, const doubl
     r.st(L.first(), 1.0);
 }
 
+template <class Row>
+RC_HD void init_row(const Row& r, const Layout& L, const double* x0, const double* mask) {
+    init_row_t(r, L, x0, mask, nullptr, nullptr);
+}
+
+template <class Row>
+RC_HD void init_row_box(const Row& r, const Layout& L, const double* x0, const double* mask, const double* lo, const double* hi) {
+    init_row_t(r, L, x0, mask, lo, hi);
+}
+
 // x + t d into the trial row
 template <int NDIM, class Row>
 RC_HD void write_trial(const Row& r, const double (&x)[NDIM], double t, const double (&d)[NDIM]) {
@@ -189,6 +212,18 @@ RCLB_UNROLL
     for (int i = 0; i < NDIM; ++i) {
         const double step = t * d[i];
         r.trial_st(i, x[i] + step);
+    }
+}
+
+// P(x + t d) into the trial row
+template <int NDIM, class Row>
+RC_HD void write_trial_box(const Row& r, const double (&x)[NDIM], double t, const double (&d)[NDIM], const double (&lo)[NDIM],
+                           const double (&hi)[NDIM]) {
+    RCLB_NO_CONTRACT
+RCLB_UNROLL
+    for (int i = 0; i < NDIM; ++i) {
+        const double step = t * d[i];
+        r.trial_st(i, clip(x[i] + step, lo[i], hi[i]));
     }
 }
 
@@ -217,13 +252,55 @@ RCLB_UNROLL
     write_trial<NDIM>(r, x, t, d);
 }
 
-// One call of `advance` for one row: (ft, gt) evaluated at the row's trial point, gt not yet masked.  Every trip count is a
-// compile-time constant; the ring is read at the run-time slot through the accessor, never through a local array.
+// the active set of a new direction: a variable on a bound whose gradient points out of the box
+template <int NDIM>
+RC_HD void active_set(const double (&x)[NDIM], const double (&g)[NDIM], const double (&lo)[NDIM], const double (&hi)[NDIM],
+                      bool (&act)[NDIM], double (&gr)[NDIM]) {
+RCLB_UNROLL
+    for (int i = 0; i < NDIM; ++i) {
+        act[i] = (x[i] <= lo[i] && g[i] > 0.0) || (x[i] >= hi[i] && g[i] < 0.0);
+        gr[i] = act[i] ? 0.0 : g[i];
+    }
+}
+
+// boxed: d = -gr (g with the active entries 0), gd = g.d, t = first_step(gr), no history, nback = 0, and the projected trial point
 template <int NDIM, class Row>
-RC_HD void advance_row(const Row& r, const Layout& L, const Params& p, double ft, double (&gt)[NDIM]) {
+RC_HD void steepest_box(const Row& r, const Layout& L, const double (&x)[NDIM], const double (&g)[NDIM], const double (&lo)[NDIM],
+                        const double (&hi)[NDIM]) {
+    bool act[NDIM];
+    double gr[NDIM], d[NDIM];
+    active_set<NDIM>(x, g, lo, hi, act, gr);
+RCLB_UNROLL
+    for (int i = 0; i < NDIM; ++i) {
+        d[i] = -gr[i];
+        r.st(L.d() + i, d[i]);
+    }
+    const double t = first_step<NDIM>(gr);
+    r.st(L.gd(), dot<NDIM>(g, d));
+    r.st(L.t(), t);
+    r.st(L.count(), 0.0);
+    r.st(L.head(), 0.0);
+    r.st(L.nback(), 0.0);
+    write_trial_box<NDIM>(r, x, t, d, lo, hi);
+}
+
+// One call of `advance` for one row: (ft, gt) evaluated at the row's trial point, gt not yet masked.  Every trip count is a
+// compile-time constant; the ring is read at the run-time slot through the accessor, never through a local array.  BOX: the boxed
+// variant, blo / bhi the row's [NDIM] bounds (read into registers once the row is known to run); otherwise they are not touched.
+template <int NDIM, bool BOX, class Row>
+RC_HD void advance_row_t(const Row& r, const Layout& L, const Params& p, double ft, double (&gt)[NDIM], const double* blo,
+                         const double* bhi) {
     RCLB_NO_CONTRACT
     if (r.ld(L.status()) != 0.0) return;                    // done: frozen, its trial row is NaN already
     const int m = L.m;
+    [[maybe_unused]] double lo[NDIM], hi[NDIM];
+    if constexpr (BOX) {
+RCLB_UNROLL
+        for (int i = 0; i < NDIM; ++i) {
+            lo[i] = blo[i];
+            hi[i] = bhi[i];
+        }
+    }
     bool gfinite = true;
 RCLB_UNROLL
     for (int i = 0; i < NDIM; ++i) {
@@ -242,10 +319,23 @@ RCLB_UNROLL
         }
         moved = true;
     } else {
-        const double f = r.ld(L.f()), t = r.ld(L.t());
-        const double ct = p.c1 * t;
-        const double slope = ct * r.ld(L.gd());
-        moved = finite(ft) && ft <= f + slope;
+        const double f = r.ld(L.f());
+        if constexpr (BOX) {                                // the slope along the projected step, which must go downhill
+            double s[NDIM], go[NDIM];
+RCLB_UNROLL
+            for (int i = 0; i < NDIM; ++i) {
+                s[i] = r.trial_ld(i) - r.ld(L.x() + i);
+                go[i] = r.ld(L.g() + i);
+            }
+            const double gs = dot<NDIM>(go, s);
+            const double slope = p.c1 * gs;
+            moved = finite(ft) && gs < 0.0 && ft <= f + slope;
+        } else {
+            const double t = r.ld(L.t());
+            const double ct = p.c1 * t;
+            const double slope = ct * r.ld(L.gd());
+            moved = finite(ft) && ft <= f + slope;
+        }
         if (moved) {                                        // accept: the pair (s, y)
             double s[NDIM], y[NDIM];
 RCLB_UNROLL
@@ -283,7 +373,10 @@ RCLB_UNROLL
             }
 RCLB_UNROLL
             for (int i = 0; i < NDIM; ++i) g[i] = r.ld(L.g() + i);
-            steepest<NDIM>(r, L, x, g);
+            if constexpr (BOX)
+                steepest_box<NDIM>(r, L, x, g, lo, hi);
+            else
+                steepest<NDIM>(r, L, x, g);
             return;
         }
         const double t = r.ld(L.t()) * 0.5;
@@ -291,7 +384,10 @@ RCLB_UNROLL
         double d[NDIM];
 RCLB_UNROLL
         for (int i = 0; i < NDIM; ++i) d[i] = r.ld(L.d() + i);
-        write_trial<NDIM>(r, x, t, d);
+        if constexpr (BOX)
+            write_trial_box<NDIM>(r, x, t, d, lo, hi);
+        else
+            write_trial<NDIM>(r, x, t, d);
         return;
     }
     // the trial point becomes the iterate
@@ -303,9 +399,19 @@ RCLB_UNROLL
         r.st(L.g() + i, g[i]);
     }
     r.st(L.f(), ft);
-    if (absmax<NDIM>(g) <= p.gtol) {
-        finish_row<NDIM>(r, L, 1);
-        return;
+    if constexpr (BOX) {                                    // the projected gradient x - P(x - g)
+        double pg[NDIM];
+RCLB_UNROLL
+        for (int i = 0; i < NDIM; ++i) pg[i] = x[i] - clip(x[i] - g[i], lo[i], hi[i]);
+        if (absmax<NDIM>(pg) <= p.gtol) {
+            finish_row<NDIM>(r, L, 1);
+            return;
+        }
+    } else {
+        if (absmax<NDIM>(g) <= p.gtol) {
+            finish_row<NDIM>(r, L, 1);
+            return;
+        }
     }
     if (!first) {
         const double fprev = r.ld(L.fprev());
@@ -326,8 +432,13 @@ RCLB_UNROLL
     const int count = (int)r.ld(L.count()), head = (int)r.ld(L.head());
     if (count > 0) {
         double q[NDIM], alpha[kMaxM];
+        [[maybe_unused]] bool act[NDIM];
+        if constexpr (BOX) {
+            active_set<NDIM>(x, g, lo, hi, act, q);
+        } else {
 RCLB_UNROLL
-        for (int i = 0; i < NDIM; ++i) q[i] = g[i];
+            for (int i = 0; i < NDIM; ++i) q[i] = g[i];
+        }
 RCLB_UNROLL
         for (int j = 0; j < kMaxM; ++j) {                   // newest first
             alpha[j] = 0.0;
@@ -385,7 +496,10 @@ RCLB_UNROLL
         }
         double d[NDIM];
 RCLB_UNROLL
-        for (int i = 0; i < NDIM; ++i) d[i] = -q[i];
+        for (int i = 0; i < NDIM; ++i) {
+            d[i] = -q[i];
+            if constexpr (BOX) d[i] = act[i] ? 0.0 : d[i];
+        }
         const double gd = dot<NDIM>(g, d);
         if (!(gd >= 0.0)) {
 RCLB_UNROLL
@@ -393,11 +507,29 @@ RCLB_UNROLL
             r.st(L.gd(), gd);
             r.st(L.t(), 1.0);
             r.st(L.nback(), 0.0);
-            write_trial<NDIM>(r, x, 1.0, d);
+            if constexpr (BOX)
+                write_trial_box<NDIM>(r, x, 1.0, d, lo, hi);
+            else
+                write_trial<NDIM>(r, x, 1.0, d);
             return;
         }
     }
-    steepest<NDIM>(r, L, x, g);                             // no pair stored, or not a descent direction: drop the history
+    // no pair stored, or not a descent direction: drop the history
+    if constexpr (BOX)
+        steepest_box<NDIM>(r, L, x, g, lo, hi);
+    else
+        steepest<NDIM>(r, L, x, g);
+}
+
+template <int NDIM, class Row>
+RC_HD void advance_row(const Row& r, const Layout& L, const Params& p, double ft, double (&gt)[NDIM]) {
+    advance_row_t<NDIM, false>(r, L, p, ft, gt, nullptr, nullptr);
+}
+
+template <int NDIM, class Row>
+RC_HD void advance_row_box(const Row& r, const Layout& L, const Params& p, double ft, double (&gt)[NDIM], const double* lo,
+                           const double* hi) {
+    advance_row_t<NDIM, true>(r, L, p, ft, gt, lo, hi);
 }
 
 }  // namespace rclb

@@ -24,6 +24,7 @@
 //                            DKW-lower variants in two passes over the K fidelities (fixed summation order).
 //   sort_*_kernel            row sort for the ECDF: merge sort in LDS (K <= 16384), chunked bitonic network above.
 //   lbfgs_advance_kernel     one LANE per controller row: the batched L-BFGS state machine (lbfgs_core.h), state [field][C]
+//   lbfgs_advance_box_kernel the same machine with box bounds: projected steps, active set in registers
 //   tail_select_kernel       one workgroup per row: list, CVaR weights and value at risk of the row's lower tail by a radix
 //                            select over an order-preserving key (no sort), compacted in index order.
 //   philox_normal_kernel     counter-based Gaussian draws for sample spaces too large to draw on the host.
@@ -1848,6 +1849,59 @@ int rc_lbfgs_advance_f64_async(int device, void* stream, int ndim, int m, long l
     switch (ndim) {
 #define RC_CASE(n) \
     case n: hipLaunchKernelGGL(lbfgs_advance_kernel<n>, grid, dim3(64), 0, s, p); break;
+        RC_CASE(3) RC_CASE(4) RC_CASE(5) RC_CASE(6) RC_CASE(7) RC_CASE(8) RC_CASE(9) RC_CASE(10) RC_CASE(11) RC_CASE(12) RC_CASE(13)
+#undef RC_CASE
+    }
+    RC_HIP_CHECK(hipGetLastError());
+    return RC_OK;
+}
+
+// ---- the boxed variant (ABI 14): box bounds lo <= x <= hi, projected steps; same state, same result entry -------------------------
+int rc_lbfgs_init_box_f64_async(int device, void* stream, int ndim, int m, long long C, const double* x0_dev, const double* mask_dev,
+                                const double* lo_dev, const double* hi_dev, double* state_dev, double* trial_dev) {
+    if (int rc = check_lbfgs(ndim, m, C)) return rc;
+    if (!lo_dev || !hi_dev) return fail(RC_EINVAL, "NULL array pointer (lo, hi: the boxed entries need both bounds)");
+    if (C == 0) return RC_OK;
+    if (!state_dev) return fail(RC_EINVAL, "NULL array pointer (state)");
+    if (!x0_dev || !trial_dev) return fail(RC_EINVAL, "NULL array pointer (x0, trial)");
+    RC_HIP_CHECK(hipSetDevice(device));
+    hipLaunchKernelGGL(lbfgs_init_box_kernel, dim3((unsigned)((C + 63) / 64)), dim3(64), 0, (hipStream_t)stream, state_dev, trial_dev,
+                       x0_dev, mask_dev, lo_dev, hi_dev, C, ndim, m);
+    RC_HIP_CHECK(hipGetLastError());
+    return RC_OK;
+}
+
+int rc_lbfgs_advance_box_f64_async(int device, void* stream, int ndim, int m, long long C, int kind, double lam, const double* row_a_dev,
+                                   const double* row_b_dev, const double* lo_dev, const double* hi_dev, double c1, double gtol,
+                                   double ftol, long long maxiter, long long maxback, double* state_dev, double* trial_dev) {
+    if (int rc = check_lbfgs(ndim, m, C)) return rc;
+    if (kind < rclb::kRaw || kind > rclb::kOneMinusPlusStd) return fail(RC_EINVAL, "kind must be 0 (raw), 1 (one_minus) or 2 (one_minus_plus_std)");
+    if (!(c1 > 0.0 && c1 < 1.0)) return fail(RC_EINVAL, "c1 must be in (0, 1)");
+    if (!(gtol >= 0.0) || !(ftol >= 0.0)) return fail(RC_EINVAL, "gtol and ftol must be non-negative");
+    if (maxiter < 1 || maxback < 0) return fail(RC_EINVAL, "maxiter must be positive and maxback non-negative");
+    if (!lo_dev || !hi_dev) return fail(RC_EINVAL, "NULL array pointer (lo, hi: the boxed entries need both bounds)");
+    if (C == 0) return RC_OK;
+    if (!state_dev) return fail(RC_EINVAL, "NULL array pointer (state)");
+    if (!row_a_dev || !trial_dev) return fail(RC_EINVAL, "NULL array pointer (row_a, trial)");
+    if (kind == rclb::kOneMinusPlusStd && !row_b_dev) return fail(RC_EINVAL, "NULL array pointer (row_b: kind 2 reads the moment rows)");
+    RC_HIP_CHECK(hipSetDevice(device));
+    LbfgsAdvanceBoxParams p{};
+    p.adv.state = state_dev;
+    p.adv.trial = trial_dev;
+    p.adv.a = row_a_dev;
+    p.adv.b = row_b_dev;
+    p.adv.C = C;
+    p.adv.m = m;
+    p.adv.kind = kind;
+    p.adv.lam = lam;
+    p.adv.opt = rclb::Params{c1, gtol, ftol, maxiter, maxback};
+    p.lo = lo_dev;
+    p.hi = hi_dev;
+    const dim3 grid((unsigned)((C + 63) / 64));
+    hipStream_t s = (hipStream_t)stream;
+    switch (ndim) {
+#define RC_CASE(n) \
+    case n: hipLaunchKernelGGL(lbfgs_advance_box_kernel<n>, grid, dim3(64), 0, s, p); break;
         RC_CASE(3) RC_CASE(4) RC_CASE(5) RC_CASE(6) RC_CASE(7) RC_CASE(8) RC_CASE(9) RC_CASE(10) RC_CASE(11) RC_CASE(12) RC_CASE(13)
 #undef RC_CASE
     }

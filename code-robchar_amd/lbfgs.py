@@ -10,13 +10,29 @@ is DONE: its `trial` row is all NaN (the gradient kernels skip a NaN controller 
 
     status   0 running                     1 max |g_i| <= gtol           2 fprev - f <= ftol max(|fprev|, |f|, 1)   (ftol = 0: off)
              3 iters = maxiter             4 line search failed          5 first value or gradient not finite, or a NaN start row
+                                                                           (boxed: or bad bounds)
 
 Bit-identity rules.  Every dot product and norm is accumulated SEQUENTIALLY over the variable index from 0.0
 (`acc = acc + a[:, i] * b[:, i]`), every product is rounded once before it is added (no fused multiply-add), divisions and
 square roots are the IEEE operations.  A NaN is a NaN: its sign and payload are not part of the definition.
 
-Bounds on the variables are out of scope: the 0 / 1 `mask` (a masked variable never moves - fix the time T this way) is the only
-constraint.
+Constraints.  The 0 / 1 `mask`: a masked variable never moves (fix the time T this way).  Box bounds: `init(x0, mask, lo, hi)` with
+`lo`, `hi` broadcastable to (C, n), -inf / +inf allowed per entry, selects the BOXED variant of the machine; without them everything
+is the unbounded machine, bit for bit.  With P(v) = where(v < lo, lo, where(v > hi, hi, v)) (a NaN stays a NaN) the boxed rules are
+
+    start     x0 <- P(x0), masked variables included; a row with a NaN bound or lo_i > hi_i is done at once with status 5
+    accept    s = trial - x, gs = g.s: accept iff ft is finite and gs < 0 and ft <= f + c1 gs (gs < 0 keeps a clipped quasi-Newton
+              step from being accepted uphill; as t -> 0 the step is t d on the free variables and gs -> t gd < 0)
+    pair      s is the projected step, y = gt - g; the store rule is unchanged
+    status 1  max_i |x_i - P(x - g)_i| <= gtol (the projected gradient of L-BFGS-B); statuses 2 to 5 are unchanged
+    direction at every new direction the active set A_i = (x_i <= lo_i and g_i > 0) or (x_i >= hi_i and g_i < 0) is recomputed;
+              gr = g with the A entries 0; the two-loop recursion starts from q = gr; dq = -q with the A entries 0, gdq = g.dq; the
+              quasi-Newton direction is taken iff count > 0 and not gdq >= 0, otherwise steepest descent -gr with first_step(gr)
+              and the history dropped; gd = g.d
+    trial     P(x + t d), on a new direction and after every halving; reject, maxback, the one-time reset and status 4 are unchanged
+
+Nothing new is stored: `lo` and `hi` are inputs of `init` and of every `advance` (the device entries take the same two arrays each
+time; this class keeps them from `init`).  L-BFGS-B's Cauchy point and subspace minimisation are out of scope.
 
 The state as the device keeps it is `state_array()`: (state_fields(n, m), C) doubles, field-major, the fields in the order of
 `field_offsets`; integers are stored as doubles."""
@@ -102,8 +118,8 @@ def objective(kind, a, b=None, lam: float = 0.0):
 
 
 class LBFGS:
-    """The state of C rows.  `init(x0, mask)` then `advance(ft, gt)` with (ft, gt) evaluated at `self.trial`, until
-    `running()` is False; the result is `x`, `f`, `g`, `status`, `iters`, `evals`."""
+    """The state of C rows.  `init(x0, mask)` - or `init(x0, mask, lo, hi)` for the boxed variant - then `advance(ft, gt)` with
+    (ft, gt) evaluated at `self.trial`, until `running()` is False; the result is `x`, `f`, `g`, `status`, `iters`, `evals`."""
 
     def __init__(self, m: int = 5, c1: float = 1e-4, gtol: float = 1e-6, ftol: float = 0.0, maxiter: int = 100, maxback: int = 20):
         if not 1 <= int(m) <= MAX_M:
@@ -111,7 +127,14 @@ class LBFGS:
         self.m, self.c1, self.gtol, self.ftol = int(m), float(c1), float(gtol), float(ftol)
         self.maxiter, self.maxback = int(maxiter), int(maxback)
 
-    def init(self, x0, mask=None):
+    def _project(self, v):
+        return np.where(v < self.lo, self.lo, np.where(v > self.hi, self.hi, v))
+
+    def _stationarity(self):
+        """what status 1 compares with gtol: max |g_i|, boxed max |x_i - P(x - g)_i|"""
+        return _absmax(self.x - self._project(self.x - self.g)) if self.box else _absmax(self.g)
+
+    def init(self, x0, mask=None, lo=None, hi=None):
         x0 = np.array(x0, dtype=np.float64)
         if x0.ndim != 2 or not MIN_DIM <= x0.shape[1] <= MAX_DIM:
             raise ValueError(f"x0: expected (C, n), n = {MIN_DIM} .. {MAX_DIM}")
@@ -119,6 +142,13 @@ class LBFGS:
         self.C, self.n = C, n
         self.mask = np.ones((C, n)) if mask is None else np.array(np.broadcast_to(np.asarray(mask, dtype=np.float64), (C, n)))
         bad = np.isnan(x0).any(axis=1)
+        self.box = lo is not None or hi is not None
+        self.lo = self.hi = None
+        if self.box:
+            self.lo = np.array(np.broadcast_to(np.asarray(-np.inf if lo is None else lo, dtype=np.float64), (C, n)))
+            self.hi = np.array(np.broadcast_to(np.asarray(np.inf if hi is None else hi, dtype=np.float64), (C, n)))
+            bad = bad | np.isnan(self.lo).any(axis=1) | np.isnan(self.hi).any(axis=1) | (self.lo > self.hi).any(axis=1)
+            x0 = self._project(x0)
         self.x = x0.copy()
         self.f = np.full(C, np.nan)
         self.g = np.full((C, n), np.nan)
@@ -165,11 +195,15 @@ class LBFGS:
             finite = np.isfinite(ft) & np.isfinite(gt).all(axis=1)
             start = first & finite
             self.status = np.where(first & ~finite, 5, self.status)
-            accept = later & np.isfinite(ft) & (ft <= self.f + (self.c1 * self.t) * self.gd)
+            s = self.trial - self.x
+            if self.box:
+                gs = _dot(self.g, s)
+                accept = later & np.isfinite(ft) & (gs < 0.0) & (ft <= self.f + self.c1 * gs)
+            else:
+                accept = later & np.isfinite(ft) & (ft <= self.f + (self.c1 * self.t) * self.gd)
             reject = later & ~accept
 
             # accept: the pair (s, y)
-            s = self.trial - self.x
             y = gt - self.g
             ss, yy, sy = _dot(s, s), _dot(y, y), _dot(s, y)
             store = accept & (sy > 0.0) & (sy >= (PAIR_EPS * np.sqrt(ss)) * np.sqrt(yy))
@@ -185,8 +219,7 @@ class LBFGS:
             self.f = np.where(moved, ft, self.f)
             self.g = np.where(moved[:, None], gt, self.g)
             self.iters = self.iters + accept
-            gmax = _absmax(self.g)
-            st1 = moved & (gmax <= self.gtol)
+            st1 = moved & (self._stationarity() <= self.gtol)
             big = np.abs(self.fprev)
             big = np.where(np.abs(self.f) > big, np.abs(self.f), big)
             big = np.where(1.0 > big, 1.0, big)
@@ -196,7 +229,12 @@ class LBFGS:
             newdir = moved & (self.status == 0)
 
             # two-loop recursion over the stored pairs: newest first, then oldest first
-            q = self.g.copy()
+            if self.box:                                   # the active set of the new direction (also of a reset's)
+                active = ((self.x <= self.lo) & (self.g > 0.0)) | ((self.x >= self.hi) & (self.g < 0.0))
+                gr = np.where(active, 0.0, self.g)
+            else:
+                gr = self.g
+            q = gr.copy()
             alpha = np.zeros((C, m))
             for j in range(m):
                 act = newdir & (j < self.count)
@@ -213,6 +251,8 @@ class LBFGS:
                 b = (1.0 / self.sy[ar, slot]) * _dot(self.Y[ar, slot], q)
                 q = np.where(act[:, None], q + (alpha[:, j] - b)[:, None] * self.S[ar, slot], q)
             dq = -q
+            if self.box:
+                dq = np.where(active, 0.0, dq)
             gdq = _dot(self.g, dq)
 
             # reject: halve, or after maxback halvings drop the history once, then give up
@@ -226,13 +266,14 @@ class LBFGS:
             steep = (newdir & ~quasi) | reset
             self.count = np.where(steep, 0, self.count)
             self.head = np.where(steep, 0, self.head)
-            ds = -self.g
+            ds = -gr
             self.d = np.where(quasi[:, None], dq, np.where(steep[:, None], ds, self.d))
             self.gd = np.where(quasi, gdq, np.where(steep, _dot(self.g, ds), self.gd))
-            self.t = np.where(quasi, 1.0, np.where(steep, first_step(self.g), self.t))
+            self.t = np.where(quasi, 1.0, np.where(steep, first_step(gr), self.t))
             self.nback = np.where(newdir | reset, 0, self.nback)
             going = run & (self.status == 0)
-            self.trial = np.where(going[:, None], self.x + self.t[:, None] * self.d, np.nan)
+            step = self.x + self.t[:, None] * self.d
+            self.trial = np.where(going[:, None], self._project(step) if self.box else step, np.nan)
         self.accepted, self.rejected = accept, reject      # (not state: for the tests' counters)
         return self
 

@@ -452,7 +452,7 @@ class noise_model_base:
         return {"cvar": total[:, 0].copy(), "grad_cvar": total[:, 1:].copy(), "var": var}
 
     def optimize_controllers(self, controllers, n_draws: int, seed: int, objective="mean", sigma=None, offset: int = 0,
-                             shared: bool = True, mask=None, max_evals: int = 60, poll: int = 8, **lbfgs_params):
+                             shared: bool = True, mask=None, max_evals: int = 60, poll: int = 8, bounds=None, **lbfgs_params):
         """Robust re-optimisation of ALL controller rows at once by the batched L-BFGS state machine on the device
         (`backend.lbfgs_init` / `lbfgs_advance`; the definition is `lbfgs.py`): per evaluation ONE gradient launch over the rows'
         trial points and one advance launch, everything device-resident on the current stream.  Objective, over `n_draws`
@@ -464,7 +464,9 @@ class noise_model_base:
 
         shared=True (common random numbers, the default): every row and every evaluation sees the same draws, so the objective is
         a deterministic function of the controller - what a line search needs.  `mask` (C, N+1) of 0 / 1 or None: a masked entry
-        never moves (mask[:, N] = 0 fixes the time T); there are no bounds on the variables.  `lbfgs_params`: m (5), c1 (1e-4),
+        never moves (mask[:, N] = 0 fixes the time T).  `bounds` = (lo, hi), each a scalar, (N+1,) or (C, N+1), NumPy or torch,
+        -inf / +inf for a side without a bound: the boxed machine - the start rows are projected into the box, every trial point
+        and the returned `x` lie inside it, and status 1 is the projected-gradient test.  `lbfgs_params`: m (5), c1 (1e-4),
         gtol (1e-6), ftol (0 = off), maxiter (100), maxback (20).  At most `max_evals` evaluations; every `poll` evaluations the
         status column is copied to the host and the loop stops when no row is running - the only synchronisation.
         Returns NumPy arrays {"x" (C, N+1), "f" (C,), "grad" (C, N+1), "status" (C,), "iters" (C,), "evals" (C,)}: the best
@@ -489,8 +491,10 @@ class noise_model_base:
             raise ValueError("n_draws, max_evals and poll must be positive")
         m = int(lbfgs_params.pop("m", 5))
         unknown = set(lbfgs_params) - set(backend.LBFGS_DEFAULTS)
+        if bounds is not None and not (isinstance(bounds, (tuple, list)) and len(bounds) == 2):
+            unknown.add("bounds")                                     # (only a pair (lo, hi) is the bounds keyword)
         if unknown:
-            raise ValueError(f"unknown L-BFGS parameters {sorted(unknown)}")
+            raise ValueError(f"unknown L-BFGS parameters {sorted(unknown)} (bounds is a pair (lo, hi))")
         if sigma is None:
             sigma = float(self.rng.args.get("scale", self.noise))
         import torch
@@ -507,8 +511,13 @@ class noise_model_base:
             mask = (mask if backend._is_torch(mask) else torch.from_numpy(np.array(np.broadcast_to(np.asarray(mask, dtype=np.float64),
                                                                                                  tuple(x0.shape)))))
             mask = mask.to(device=dev, dtype=torch.float64).contiguous()
+        box = {}
+        if bounds is not None:                                        # on the device once, the same two tensors at every call
+            as_rows = lambda b: (b if backend._is_torch(b) else torch.from_numpy(np.array(b, dtype=np.float64))).to(
+                device=dev, dtype=torch.float64).expand(tuple(x0.shape)).contiguous()
+            box = {"bounds": (as_rows(bounds[0]), as_rows(bounds[1]))}
         geo = dict(h0_diag=diag, h0_offdiag=off)
-        state, trial = backend.lbfgs_init(x0, mask, m=m)
+        state, trial = backend.lbfgs_init(x0, mask, m=m, **box)
         status = state[lbfgs.field_offsets(N + 1, m)["status"]]
         for ev in range(1, int(max_evals) + 1):
             row_b = None
@@ -520,7 +529,7 @@ class noise_model_base:
                                                       shared=shared, want=want, **geo)
                 row_a, row_b = res["mean"], res.get("moment")
             backend.lbfgs_advance(state, trial, row_a, row_b, m=m, kind="one_minus" if kind == "cvar" else kind, lam=par,
-                                  **lbfgs_params)
+                                  **box, **lbfgs_params)
             if ev % int(poll) == 0 and ev < int(max_evals) and not bool((status == 0.0).any().item()):
                 break
         res = backend.lbfgs_result(state, trial, m=m)

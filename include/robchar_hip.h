@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 13      /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 14      /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -65,7 +65,8 @@ extern "C" {
                                   11: + rc_mc_fidelity_grad_listed_f64_async (additive);
                                   12: + rc_tail_select_len, rc_tail_select_f64_async (additive);
                                   13: + rc_lbfgs_state_len, rc_lbfgs_init_f64_async, rc_lbfgs_advance_f64_async,
-                                      rc_lbfgs_result_f64_async (additive) */
+                                      rc_lbfgs_result_f64_async (additive);
+                                  14: + rc_lbfgs_init_box_f64_async, rc_lbfgs_advance_box_f64_async (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -354,8 +355,9 @@ int rc_tail_select_f64_async(int device, void* stream, const double* fid_dev, lo
  *     trial_dev [C][ndim]: the `controllers_dev` argument of the next gradient launch.  The row of a DONE row is all NaN, which the
  *               gradient entries skip (their NaN-row rule); a done row's state never changes again.
  * rc_lbfgs_init_f64_async: x0_dev [C][ndim] start rows; mask_dev [C][ndim] of 0.0 / 1.0 or NULL (= all free): the gradient is
- *     multiplied by it, so a masked variable never moves (fix T this way).  Bounds on the variables are not supported.  A start row
- *     with a NaN is done at once (status 5).
+ *     multiplied by it, so a masked variable never moves (fix T this way).  Bounds on the variables are not supported by this
+ *     entry and rc_lbfgs_advance_f64_async: the boxed entries (ABI 14) below take them.  A start row with a NaN is done at once
+ *     (status 5).
  * rc_lbfgs_advance_f64_async: one (value, gradient) per row, evaluated at trial_dev, from row_a_dev [C][ndim + 1]:
  *     kind 0  raw                  (f, g_0 .. g_{ndim-1}) as they are
  *     kind 1  one_minus            row_a = a `mean_out` row of the gradient entries or a `sum_out` row of the listed entry:
@@ -383,6 +385,32 @@ int rc_lbfgs_advance_f64_async(int device, void* stream, int ndim, int m, long l
 int rc_lbfgs_result_f64_async(int device, void* stream, int ndim, int m, long long C, const double* state_dev, double* x_out_dev,
                               double* f_out_dev, double* g_out_dev, int* status_out_dev, long long* iters_out_dev,
                               long long* evals_out_dev);
+
+/* (ABI 14) The BOXED variant of the batched L-BFGS: box bounds lo <= x <= hi per variable and row, by projected steps.  The same
+ * state (rc_lbfgs_state_len, layout unchanged: nothing new is stored), the same trial_dev and NaN-row rule, the same kinds,
+ * parameters and statuses, and rc_lbfgs_result_f64_async reads the result; the unbounded entries above are untouched (their
+ * kernels, arithmetic and bits).  A state started by rc_lbfgs_init_box_f64_async is advanced by rc_lbfgs_advance_box_f64_async only.
+ *     lo_dev, hi_dev  [C][ndim] like x0_dev, both required (NULL: RC_EINVAL before any HIP call); -inf / +inf per entry for a side
+ *                     without a bound.  They are inputs, not state: hand the SAME two arrays to init and to every advance.
+ * With P(v) = v < lo ? lo : (v > hi ? hi : v) (a NaN stays a NaN), the rules that differ from the unbounded machine (the
+ * definition is again code-robchar_amd/lbfgs.py, the same bit rules):
+ *     start      x0 <- P(x0), masked variables included; a row with a NaN bound or lo_i > hi_i is done at once with status 5
+ *     accept     s = trial - x, gs = g.s: accepted iff f_trial is finite and gs < 0 and f_trial <= f + c1 gs
+ *     pair       s is the projected step, y = g_trial - g; the store rule is unchanged
+ *     status 1   max_i |x_i - P(x - g)_i| <= gtol (the projected gradient of L-BFGS-B)
+ *     direction  at every new direction the active set A_i = (x_i <= lo_i and g_i > 0) or (x_i >= hi_i and g_i < 0) is recomputed;
+ *                the two-loop recursion starts from g with the A entries 0, the A entries of its result are set to 0, and it is
+ *                taken iff a pair is stored and g.d < 0; otherwise steepest descent along -g with the A entries 0 (first step
+ *                min(1, 1 / |that vector|_2)) and the history is dropped
+ *     trial      P(x + t d), on a new direction and after every halving; reject, maxback, the one reset and status 4 as above
+ * Every trial point and every iterate lies inside the box exactly, and an accepted value is never above its predecessor.
+ * Not L-BFGS-B: no Cauchy point, no subspace minimisation.  Argument checks, C = 0 and the enqueue-only contract as for ABI 13. */
+int rc_lbfgs_init_box_f64_async(int device, void* stream, int ndim, int m, long long C, const double* x0_dev, const double* mask_dev,
+                                const double* lo_dev, const double* hi_dev, double* state_dev, double* trial_dev);
+int rc_lbfgs_advance_box_f64_async(int device, void* stream, int ndim, int m, long long C, int kind, double lam,
+                                   const double* row_a_dev, const double* row_b_dev, const double* lo_dev, const double* hi_dev,
+                                   double c1, double gtol, double ftol, long long maxiter, long long maxback,
+                                   double* state_dev, double* trial_dev);
 
 /* (ABI 6) 1 when the kernel above is the faster of the two bit-identical routes for this geometry (N <= 13, or N = 14 with
  * {in, out} = {0, N-1}), else 0; 0 everywhere when ROBCHAR_PHILOX_FUSED=0 is in the environment (read per call).  The ONE

@@ -11,7 +11,17 @@ restarts from the same start rows before its timed stretch, with gtol = 0 and a 
 Beside it: the value scripts/robust_lbfgs.py (SciPy L-BFGS-B, one row) reaches on the first shipped 0 -> 6 controller with the
 evaluation budget the batched loop gives every row (printed, not asserted).
 
-    python scripts/lbfgs_bench.py [--out profiles/lbfgs_bench.txt] [--evals 200] [--warm 20] [--repeats 3]"""
+--box: instead of (c), the BOXED machine under the same protocol, alternated with (a) and (b) in the same process:
+
+  (d) gradient launch + `backend.lbfgs_advance(bounds=...)` in the box [-W, W]^N x [T0 - 1, T0 + 0.5] around the start rows
+      (--box-width W, default 0.35; biases U(-0.5, 0.5): at 0.35 three in ten start outside and are projected, so rows sit on bounds
+      while they step; at 1.0 the bounds are touched rarely),
+
+reported against (b) of the same run, with the number of rows still running at the end of (b) and of (d): a row that has ended is a
+NaN row, which the gradient kernel skips, so a route with fewer running rows does less gradient work.
+
+    python scripts/lbfgs_bench.py [--out profiles/lbfgs_bench.txt] [--evals 200] [--warm 20] [--repeats 3]
+    python scripts/lbfgs_bench.py --box --out profiles/lbfgs_box_bench.txt"""
 import argparse
 import importlib
 import os
@@ -129,6 +139,8 @@ def main():
     ap.add_argument("--warm", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--no-scipy", action="store_true")
+    ap.add_argument("--box", action="store_true", help="time the boxed advance (d) beside (a) and (b) instead of the torch route (c)")
+    ap.add_argument("--box-width", type=float, default=0.35)
     args = ap.parse_args()
     import torch
     import chain_checks as cc
@@ -138,6 +150,12 @@ def main():
              f"objective mean, sigma = 0.05, shared draws, m = 5; {args.evals} evaluations after {args.warm}, routes alternated, "
              f"{args.repeats} repeats (min .. max), HIP events",
              "#  N      C       K | (a) grad us | (b) grad + advance us | (c) grad + torch us | (b)/(a) | (b)/(c) (of the minima) | (c) check"]
+    if args.box:
+        lines = [f"# per evaluation, us: (a) gradient launch alone, (b) + backend.lbfgs_advance, (d) + backend.lbfgs_advance(bounds=...), box "
+                 f"[-{args.box_width}, {args.box_width}]^N x [T0 - 1, T0 + 0.5]; objective mean, sigma = 0.05, shared draws, m = 5; {args.evals} evaluations after "
+                 f"{args.warm}, routes alternated, {args.repeats} repeats (min .. max), HIP events",
+                 "#  N      C       K | (a) grad us | (b) grad + advance us | (d) grad + boxed advance us | (b)/(a) | (d)/(b) (of the minima) | "
+                 "(d) entries on a bound; rows running at the end of (b), of (d)"]
     params = dict(gtol=0.0, maxiter=10 ** 9)
 
     def timed(step, n):
@@ -162,6 +180,19 @@ def main():
                 step_b = lambda: be.lbfgs_advance(state, trial, grad(trial), None, m=5, kind="one_minus", **params)
                 timed(step_b, args.warm)
                 tb.append(timed(step_b, args.evals))
+                if args.box:
+                    lo, hi = torch.full_like(x0, -args.box_width), torch.full_like(x0, args.box_width)
+                    lo[:, N], hi[:, N] = x0[:, N] - 1.0, x0[:, N] + 0.5
+                    bstate, btrial = be.lbfgs_init(x0, None, m=5, bounds=(lo, hi))
+                    step_d = lambda: be.lbfgs_advance(bstate, btrial, grad(btrial), None, m=5, kind="one_minus", bounds=(lo, hi), **params)
+                    timed(step_d, args.warm)
+                    tc.append(timed(step_d, args.evals))
+                    if rep == 0:
+                        res = be.lbfgs_result(bstate, btrial, m=5, want=("x", "status"))
+                        run_b = int((be.lbfgs_result(state, trial, m=5, want=("status",))["status"] == 0).sum())
+                        check = (f"{int(((res['x'] == lo) | (res['x'] == hi)).sum())} of {res['x'].numel()}; "
+                                 f"{run_b}, {int((res['status'] == 0).sum())} of {C}")
+                    continue
                 tm = TorchLBFGS(x0, m=5)
                 step_c = lambda: tm.advance(grad(tm.trial))
                 timed(step_c, args.warm)
@@ -170,9 +201,10 @@ def main():
                     fb = be.lbfgs_result(state, trial, m=5, want=("f",))["f"]
                     check = f"max |f_b - f_c| = {float((fb - tm.f).abs().max()):.1e}"
             fmt = lambda t: f"{min(t):8.1f} .. {max(t):8.1f}"
-            lines.append(f"  {N:2d} {C:6d} {K:7d} | {fmt(ta)} | {fmt(tb)} | {fmt(tc)} | {min(tb) / min(ta):6.3f} | {min(tb) / min(tc):6.3f} | {check}")
+            last = min(tc) / min(tb) if args.box else min(tb) / min(tc)
+            lines.append(f"  {N:2d} {C:6d} {K:7d} | {fmt(ta)} | {fmt(tb)} | {fmt(tc)} | {min(tb) / min(ta):6.3f} | {last:6.3f} | {check}")
             print(lines[-1], flush=True)
-    if not args.no_scipy:
+    if not args.no_scipy and not args.box:
         try:
             batched = importlib.import_module("robust_lbfgs_batched").run(rows=1, evals=60, verbose=False)
             scipy_run = importlib.import_module("robust_lbfgs").run(row=0, maxiter=60, train=1000, verbose=False, draws="philox")

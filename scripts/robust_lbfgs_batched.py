@@ -4,10 +4,13 @@
 but the status column ever returns to the host.  scripts/robust_lbfgs.py does one row through SciPy.
 
     python scripts/robust_lbfgs_batched.py [--rows 57] [--sigma 0.05] [--evals 60] [--train 1000] [--pair 0-6] [--risk LAM | --cvar ALPHA]
+                                            [--box BMAX TMAX]
 
 The objective is 1 - mean F (--risk LAM: + LAM std F; --cvar ALPHA: 1 - CVaR_ALPHA F) over `train` shared counter-based draws
 (common random numbers); the test figure of a row is 1 - mean F over 10 000 draws of the same stream behind the training draws.
-Prints start / final / test value per row; `run()` returns them for callers (tests)."""
+--box BMAX TMAX: the boxed machine with |bias| <= BMAX and 0 <= T <= TMAX (the shipped controllers are box-constrained results: 10
+and 30); per row the largest bound violation of the result (which must be 0) and the number of variables that end on a bound are
+printed too.  Prints start / final / test value per row; `run()` returns them for callers (tests)."""
 import argparse
 import importlib
 import os
@@ -20,7 +23,8 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 
-def run(rows=None, sigma=0.05, evals=60, train=1000, pair="0-6", verbose=True, risk=0.0, cvar=None, seed=0x5EED0010, **lbfgs_params):
+def run(rows=None, sigma=0.05, evals=60, train=1000, pair="0-6", verbose=True, risk=0.0, cvar=None, seed=0x5EED0010, box=None,
+        **lbfgs_params):
     if cvar is not None and risk != 0.0:
         raise ValueError("cvar and risk are two objectives: give one of them")
     noise = importlib.import_module("code-robchar_amd.noise")
@@ -36,16 +40,25 @@ def run(rows=None, sigma=0.05, evals=60, train=1000, pair="0-6", verbose=True, r
             return 1.0 - nm.fidelity_cvar_philox(x, n_draws, seed, cvar, sigma=sigma, offset=offset, shared=True)["cvar"]
         mo = nm.fidelity_moments_philox(x, n_draws, seed, sigma=sigma, offset=offset, shared=True)
         return 1.0 - mo["fav"] + risk * mo["std"]
+    if box is not None:
+        bmax, tmax = (float(v) for v in box)
+        lo, hi = np.full(8, -bmax), np.full(8, bmax)
+        lo[7], hi[7] = 0.0, tmax
+        lbfgs_params["bounds"] = (lo, hi)
+        x0 = np.clip(x0, lo, hi)                          # (what the boxed machine starts from: `start` is its value)
     start = value(x0, train, 0)
     res = nm.optimize_controllers(x0, train, seed, objective=objective, sigma=sigma, shared=True, max_evals=evals, **lbfgs_params)
+    if box is not None:
+        res["violation"] = np.maximum(np.maximum(lo - res["x"], res["x"] - hi), 0.0).max(axis=1)
+        res["on_bound"] = ((res["x"] == lo) | (res["x"] == hi)).sum(axis=1)
     test_start, test_final = (1.0 - nm.fidelity_moments_philox(x, 10000, seed, sigma=sigma, offset=train * 7 * 3, shared=True)["fav"]
                               for x in (x0, res["x"]))
     if verbose:
         print(f"# objective {objective}, sigma = {sigma}, {train} shared draws, at most {evals} evaluations; test: 1 - mean F over 10 000 draws")
-        print("# row      start        final   test start   test final  status iters evals")
+        print("# row      start        final   test start   test final  status iters evals" + ("  violation on_bound" if box else ""))
         for c in range(x0.shape[0]):
             print(f"{c:5d} {start[c]:12.8f} {res['f'][c]:12.8f} {test_start[c]:12.8f} {test_final[c]:12.8f} {res['status'][c]:7d} "
-                  f"{res['iters'][c]:5d} {res['evals'][c]:5d}")
+                  f"{res['iters'][c]:5d} {res['evals'][c]:5d}" + (f" {res['violation'][c]:10.3g} {res['on_bound'][c]:8d}" if box else ""))
         print(f"# mean   {start.mean():12.8f} {res['f'].mean():12.8f} {test_start.mean():12.8f} {test_final.mean():12.8f}")
     return {"x0": x0, "start": start, "test_start": test_start, "test_final": test_final, "model": nm, "objective": objective, **res}
 
@@ -60,5 +73,6 @@ if __name__ == "__main__":
     goal = ap.add_mutually_exclusive_group()
     goal.add_argument("--risk", type=float, default=0.0)
     goal.add_argument("--cvar", type=float, default=None, metavar="ALPHA")
+    ap.add_argument("--box", type=float, nargs=2, default=None, metavar=("BMAX", "TMAX"))
     args = ap.parse_args()
-    run(args.rows, args.sigma, args.evals, args.train, args.pair, risk=args.risk, cvar=args.cvar)
+    run(args.rows, args.sigma, args.evals, args.train, args.pair, risk=args.risk, cvar=args.cvar, box=args.box)
