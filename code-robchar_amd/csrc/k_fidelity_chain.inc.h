@@ -110,7 +110,9 @@ __global__ __launch_bounds__(64, fid_min_waves(N, MODE)) void mc_fid_chain_kerne
     // HBM -> LDS -> registers.  The tile's draws are one contiguous run of nk*G doubles.  Each phase copies
     // SP samples into LDS by LDS-DMA (global_load_lds: no staging VGPRs, fully coalesced, every HBM byte
     // fetched once; 16-byte pieces when the run is 16-byte aligned and sized, 4-byte pieces otherwise) and
-    // the SP lanes that own them read their G values back (the transposition).
+    // the SP lanes that own them read their G values back (the transposition).  The draws are read once and are larger
+    // than L2: the loads carry the streaming policy rckp::kDrawLoadAux (`nt`) - the first round's burst, which every
+    // launch waits for, lands in 3.8 us instead of 5.8 (profiles/launch_boundary_simd.txt).
     const char* src = (const char*)(p.draws + c * p.draw_cstride + kb * G);
     // (no initialisation: every lane < nk reads its G values in exactly one phase, lanes >= nk never use theirs -
     // zeroing them was 2 G v_mov_b32 per wave)
@@ -128,7 +130,7 @@ __global__ __launch_bounds__(64, fid_min_waves(N, MODE)) void mc_fid_chain_kerne
                     const int off = it * 1024 + lane * 16;
                     if (off < bytes)
                         __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off),
-                                                         (rc_lptr_t)((char*)stage + it * 1024), 16, 0, 0);
+                                                         (rc_lptr_t)((char*)stage + it * 1024), 16, 0, rckp::kDrawLoadAux);
                 }
             } else {
 #pragma unroll 2
@@ -136,7 +138,7 @@ __global__ __launch_bounds__(64, fid_min_waves(N, MODE)) void mc_fid_chain_kerne
                     const int off = it * 256 + lane * 4;
                     if (off < bytes)
                         __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off),
-                                                         (rc_lptr_t)((char*)stage + it * 256), 4, 0, 0);
+                                                         (rc_lptr_t)((char*)stage + it * 256), 4, 0, rckp::kDrawLoadAux);
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // DMA landed
@@ -218,20 +220,40 @@ __global__ __launch_bounds__(64, fid_min_waves(N, MODE)) void mc_fid_chain_kerne
             }
         }
     }
-    if (lane < nk) dst[lane] = f;
+    // The fidelities are written once and read by the NEXT kernel (the reduction).  On launches near the benchmark's size the
+    // non-temporal store is worth 0.3 - 1 % beside the streaming loads and nothing on large ones: a wave-uniform choice
+    // of the host (the rule and its sweep: launch_chain), same bits either way.
+    if (lane < nk) {
+        if (p.nt_store) {
+            // (the address is opaque to the optimiser: it otherwise merges the two stores of the same value to the same
+            // address into ONE plain store and drops the policy)
+            __attribute__((address_space(1))) double* nt_dst = (__attribute__((address_space(1))) double*)(dst + lane);
+            asm volatile("" : "+v"(nt_dst));
+            __builtin_nontemporal_store(f, nt_dst);
+        } else {
+            dst[lane] = f;
+        }
+    }
 
 #ifdef RC_STAMPS
     __builtin_amdgcn_s_waitcnt(0);
     const long long t_end = __builtin_amdgcn_s_memtime();
     if (lane == 0 && p.stamps) {
-        p.stamps[blockIdx.x * 8 + 0] = t_begin;
-        p.stamps[blockIdx.x * 8 + 1] = t_loaded;
-        p.stamps[blockIdx.x * 8 + 2] = t_end;
-        p.stamps[blockIdx.x * 8 + 3] = __builtin_amdgcn_s_memrealtime() - r_begin;
-        p.stamps[blockIdx.x * 8 + 4] = t_ctrl;
-        p.stamps[blockIdx.x * 8 + 5] = t_ph[0];
-        p.stamps[blockIdx.x * 8 + 6] = t_in[0];     // QL starts
-        p.stamps[blockIdx.x * 8 + 7] = t_in[1];     // QL done
+        long long* rec = p.stamps + tile * rckp::kStampSlots;      // by tile: valid under any launch geometry
+        rec[0] = t_begin;
+        rec[1] = t_loaded;
+        rec[2] = t_end;
+        rec[3] = __builtin_amdgcn_s_memrealtime() - r_begin;
+        rec[4] = t_ctrl;
+        rec[5] = t_ph[0];
+        rec[6] = t_in[0];     // QL starts
+        rec[7] = t_in[1];     // QL done
+        // where the wave ran: HW_ID (register 4: wave slot [3:0], SIMD [5:4], CU [11:8], shader array [12], shader engine
+        // [15:13]) and XCC_ID (register 20: XCD [3:0]); reads of the hardware id registers
+        rec[8] = (long long)__builtin_amdgcn_s_getreg(4 | (0 << 6) | (31 << 11));
+        rec[9] = (long long)__builtin_amdgcn_s_getreg(20 | (0 << 6) | (31 << 11));
+        rec[10] = r_begin;    // the chip-wide 100 MHz clock: comparable between compute units and between launches
+        rec[11] = r_begin + rec[3];
     }
 #endif
 }
@@ -265,14 +287,14 @@ __device__ __forceinline__ void stage_tile_draws(const char* src, int nk, int la
                 for (int it = 0; it < (kPhaseBytes + 1023) / 1024; ++it) {
                     const int off = it * 1024 + lane * 16;
                     if (off < bytes)
-                        __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off), (rc_lptr_t)((char*)stage + it * 1024), 16, 0, 0);
+                        __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off), (rc_lptr_t)((char*)stage + it * 1024), 16, 0, rckp::kDrawLoadAux);
                 }
             } else {
 #pragma unroll 2
                 for (int it = 0; it < (kPhaseBytes + 255) / 256; ++it) {
                     const int off = it * 256 + lane * 4;
                     if (off < bytes)
-                        __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off), (rc_lptr_t)((char*)stage + it * 256), 4, 0, 0);
+                        __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off), (rc_lptr_t)((char*)stage + it * 256), 4, 0, rckp::kDrawLoadAux);
                 }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");

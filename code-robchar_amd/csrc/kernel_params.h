@@ -11,6 +11,16 @@ struct StaticH {          // passed by value in the kernarg segment: no device a
     double off[RC_MAX_NSPIN];
 };
 
+// Cache policy of the draw stream: the `aux` operand of the LDS-DMA loads (__builtin_amdgcn_global_load_lds) of
+// mc_fid_chain_kernel and stage_tile_draws.  The draws are read exactly once per launch and are larger than L2 (168 MB at
+// 100 x 10 000, N = 7), so they stream: 2 = the `nt` bit (global_load_lds_dword[x4] ... nt), 0 = the default policy.
+// Changes no arithmetic (profiles/launch_boundary_ab.txt).  -DRC_DRAW_LOAD_AUX=0 builds the other side for A/B timing
+// (scripts/build_variant.sh).
+#ifndef RC_DRAW_LOAD_AUX
+#define RC_DRAW_LOAD_AUX 2
+#endif
+constexpr int kDrawLoadAux = RC_DRAW_LOAD_AUX;
+
 struct FidParams {
     const double* ctrl;    // [C][N+1]
     const double* draws;   // [C][K][N][3]
@@ -21,9 +31,11 @@ struct FidParams {
     long long ntiles;           // C * tiles_per_ctrl
     int in, out;
     int align16;                // draws base and every controller's run of K*3N doubles are 16-byte aligned
+    int nt_store;               // mc_fid_chain_kernel: the fidelities leave with a non-temporal store (host rule: launch_chain)
     StaticH h0;
-    long long* stamps;          // diagnostic builds only (-DRC_STAMPS): [ntiles][8] s_memtime stamps
+    long long* stamps;          // diagnostic builds only (-DRC_STAMPS): [ntiles][kStampSlots] stamps, indexed by tile
 };
+constexpr int kStampSlots = 12; // (RC_STAMPS) slots of one tile's record: mc_fid_chain_kernel lists them where it writes them
 
 // repair list of the ring-topology route (mc_fid_ring_mixed_kernel -> mc_fid_ring_repair_kernel)
 struct RingRepairList {

@@ -286,10 +286,23 @@ RingBuf& ring_buf_for(DeviceCtx& ctx, hipStream_t s) {
     return it->second;
 }
 
+// Store rule of mc_fid_chain_kernel: launches of fewer than this many tiles write their fidelities with non-temporal stores.
+// scripts/nt_store_sweep.py (N = 7, K = 10 000, rule forced on / off, interleaved; profiles/launch_boundary_ab.txt section 3),
+// non-temporal / plain time per launch, end-to-end pair | general pair:
+//     3 925 tiles 0.970 | 0.976      15 700 (the benchmark's launch) 0.987 | 0.991      62 800 tiles 0.997 | 0.996
+//     157 000 .. 1 570 000 tiles 0.995 .. 1.0015, every one inside the two sides' own spread (0.2 .. 1.7 %)
+// The gain belongs to the launch boundary and is gone where the boundary is: from 62 800 tiles on nothing is measurable, and an
+// earlier trial read +1.6 % on a launch of 10^8 evaluations (NOTEBOOK.md 12 (i)).  The threshold sits between the last size with a
+// measured gain and the first one without: 32 768 tiles = eight rounds of the chip's 4 096 wave slots.
+constexpr long long kNtStoreTiles = 32768;
+std::atomic<long long> g_nt_store_tiles{kNtStoreTiles};      // (tests move it: rc_debug_nt_store_tiles)
+
 template <int N, int MODE>
-int launch_chain(hipStream_t s, const FidParams& p) {
-    const long long blocks = p.ntiles;
+int launch_chain(hipStream_t s, const FidParams& p0, long long nt_store_tiles) {
+    const long long blocks = p0.ntiles;
     if (blocks > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    FidParams p = p0;
+    p.nt_store = (blocks < nt_store_tiles) ? 1 : 0;
     hipLaunchKernelGGL((mc_fid_chain_kernel<N, MODE>), dim3((unsigned)blocks), dim3(64), 0, s, p);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
@@ -466,16 +479,17 @@ int enqueue_fidelity(hipStream_t s, int kernel, int N, int in, int out, const do
             RC_HIP_CHECK((hipError_t)rc_large_chain_launch(N, (void*)s, &p));
             return RC_OK;
         }
+        const long long nt_tiles = g_nt_store_tiles.load(std::memory_order_relaxed);
         switch (N) {
 #define RC_CASE(n)                                                                        \
     case n:                                                                               \
-        return mode == rc::kWeightsRows ? launch_chain<n, rc::kWeightsRows>(s, p)         \
-               : (mode == rc::kWeightsEnds ? launch_chain<n, rc::kWeightsEnds>(s, p)      \
-                                           : launch_chain<n, rc::kWeightsAdjugate>(s, p));
+        return mode == rc::kWeightsRows ? launch_chain<n, rc::kWeightsRows>(s, p, nt_tiles)         \
+               : (mode == rc::kWeightsEnds ? launch_chain<n, rc::kWeightsEnds>(s, p, nt_tiles)      \
+                                           : launch_chain<n, rc::kWeightsAdjugate>(s, p, nt_tiles));
 /* N = 15, 16: no end-to-end instantiation (never dispatched: see above) */
 #define RC_CASE_ADJ_ROWS(n)                                                               \
     case n:                                                                               \
-        return mode == rc::kWeightsRows ? launch_chain<n, rc::kWeightsRows>(s, p) : launch_chain<n, rc::kWeightsAdjugate>(s, p);
+        return mode == rc::kWeightsRows ? launch_chain<n, rc::kWeightsRows>(s, p, nt_tiles) : launch_chain<n, rc::kWeightsAdjugate>(s, p, nt_tiles);
 #ifdef RC_DEV_FEW_N      /* kernel-tuning builds only (scripts/): the three BASELINE sizes, a third of the compile time */
             RC_CASE(5) RC_CASE(7) RC_CASE(10)
 #else
@@ -1478,9 +1492,15 @@ static int blocking_deriv(decltype(&enqueue_grad) enqueue, int per_sample, int p
 extern "C" {
 
 #ifdef RC_STAMPS
-// diagnostic builds only: device buffer of [ntiles][4] int64 receiving per-wave s_memtime stamps
+// diagnostic builds only: device buffer of [ntiles][rckp::kStampSlots] int64 receiving per-wave stamps; read when a launch is
+// ENQUEUED, so two launches enqueued back to back can write two buffers
 int rc_debug_set_stamps(long long* dev_buf) { g_stamps = dev_buf; return 0; }
 #endif
+
+// Test and measurement hook, not part of the C ABI (not in robchar_hip.h): moves the tile count below which launch_chain picks
+// the non-temporal fidelity store (0: never, a negative value: back to the built-in rule) and returns the value it replaced.
+// tests/test_gpu_launch_boundary.py runs both sides of the rule on the same inputs with it.
+long long rc_debug_nt_store_tiles(long long tiles) { return g_nt_store_tiles.exchange(tiles < 0 ? kNtStoreTiles : tiles); }
 
 int rc_version(void) { return RC_ABI_VERSION; }
 
@@ -1948,6 +1968,8 @@ int rc_mc_fidelity_philox_f64_async(int device, void* stream, int kernel, int N,
     p.in = in;
     p.out = out;
     p.align16 = 0;
+    // (no store rule here: the fused kernel has no draw stream for the non-temporal store to protect, and its A/B with the rule
+    // on and off read 0.994 .. 1.009 at N = 5, 7, 10 and 25 .. 1 000 controllers - profiles/launch_boundary_ab.txt section 4)
     fill_h0(p.h0, N, h0_diag, h0_offdiag);
     PhiloxDraws q{seed, offset, sigma_rows_dev, sigma};
     hipStream_t s = (hipStream_t)stream;

@@ -14,12 +14,19 @@ draws = torch.from_numpy(0.05 * rng.standard_normal((C, K, N, 3))).cuda()
 ct = torch.from_numpy(ctrl).cuda()
 out = torch.empty((C, K), dtype=torch.float64, device="cuda")
 ntiles = (C * ((K + 63) // 64) + TPW - 1) // TPW
-st = torch.zeros((ntiles, 8), dtype=torch.int64, device="cuda")
-lib.rc_debug_set_stamps(ctypes.c_void_p(st.data_ptr()))
-for _ in range(3):
+if os.environ.get("NT_STORE_TILES"):         # the store rule of launch_chain, e.g. 0 = plain stores (the hook is not part of the C ABI)
+    lib.rc_debug_nt_store_tiles.argtypes, lib.rc_debug_nt_store_tiles.restype = [ctypes.c_longlong], ctypes.c_longlong
+    lib.rc_debug_nt_store_tiles(int(os.environ["NT_STORE_TILES"]))
+SLOTS = 12                                 # rckp::kStampSlots: 8 .. 11 = HW_ID, XCC_ID, begin and end on the chip-wide clock
+st = torch.zeros((2, ntiles, SLOTS), dtype=torch.int64, device="cuda")
+# the buffer is read when a launch is enqueued: three warm launches, then TWO back-to-back launches into a buffer each (the second
+# one's first wave against the first one's last: scripts/stamps_timeline.py)
+for j in (0, 0, 0, 0, 1):
+    lib.rc_debug_set_stamps(ctypes.c_void_p(st[j].data_ptr()))
     be.mc_fidelity(ct, draws, N, 0, N - 1, out=out)
 torch.cuda.synchronize()
-s = st.cpu().numpy()
+both = st.cpu().numpy()
+s = both[0]
 life = s[:, 2] - s[:, 0]; load = s[:, 1] - s[:, 0]; comp = s[:, 2] - s[:, 1]
 real = s[:, 3] / 100e6
 print(f"shader clock from per-wave ticks/realtime: median {np.median(life / real) / 1e9:.3f} GHz (p10 {np.percentile(life/real,10)/1e9:.3f}, p90 {np.percentile(life/real,90)/1e9:.3f}); wave lifetime median {np.median(real)*1e6:.1f} us")
@@ -35,4 +42,4 @@ print(f"kernel span {span_ticks} ticks; realtime span {span_real*1e6:.1f} us -> 
 print(f"sum of wave lifetimes / span = {life.sum()/span_ticks:.1f} (avg resident waves chip-wide; /1024 SIMDs = {life.sum()/span_ticks/1024:.2f} per SIMD)")
 if os.environ.get("DUMP"):
     os.makedirs(os.path.dirname(os.environ["DUMP"]), exist_ok=True)
-    np.save(os.environ["DUMP"], s)
+    np.save(os.environ["DUMP"], both)

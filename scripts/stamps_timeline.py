@@ -7,12 +7,20 @@ s_memtime counts per CU (the 256 counters are not synchronised), so tiles are gr
 
 usage: python3 scripts/stamps_timeline.py gpurun_out/<label>/stamps_n7.npy [--ghz 1.95]
 columns of the dump (per tile): 0 begin, 1 staged, 2 end (s_memtime ticks), 3 realtime ticks of the wave (100 MHz), 4 ctrl row read,
-5 first staging phase landed, 6 QL starts, 7 QL done
+5 first staging phase landed, 6 QL starts, 7 QL done, 8 HW_ID (wave slot [3:0], SIMD [5:4], CU [11:8], SH [12], SE [15:13]),
+9 XCC_ID (XCD [3:0]), 10 / 11 begin / end on the chip-wide 100 MHz clock (comparable between units and between launches)
+
+With columns 8 .. 11 (records indexed by tile) a second part follows - the DRAIN per SIMD: waves of a compute unit are told apart
+by the hardware ids instead of by counter base, and for every unit the resident and computing waves of each of its four SIMDs over
+the last 12 us, the end time of each SIMD, the spread of the units' end times over the chip and, from a dump of two back-to-back
+launches, the gap between the last unit's end and the next launch's first wave.
 """
 import sys
 import numpy as np
 
-s = np.load(sys.argv[1]).astype(np.int64)
+raw = np.load(sys.argv[1]).astype(np.int64)
+both = raw if raw.ndim == 3 else raw[None]             # (launches, tiles, slots): scripts/stamps.py dumps two back-to-back launches
+s = both[0]
 life_us = s[:, 3] / 100.0
 tick = float(np.median((s[:, 2] - s[:, 0]) / np.maximum(life_us, 1e-9)))          # ticks per us, from the waves' own realtime
 if "--ghz" in sys.argv:
@@ -46,3 +54,83 @@ area = np.mean([(a[2] - a[1]).sum() for a in agg])
 span = med(lambda a: a[2].max())
 print(f"  computing waves in steady state {steady:.1f} per unit; compute-time integral / (span x steady) = {area / (span * steady):.3f} "
       f"-> {span * (1 - area / (span * steady)):.1f} us of the {span:.1f} us span are fill + drain")
+
+# ------------------------------------------------------------------------------------------------------------------------
+# the drain per SIMD (columns 8 .. 11)
+# ------------------------------------------------------------------------------------------------------------------------
+if s.shape[1] < 12:
+    sys.exit(0)
+
+
+def units_of(rec):
+    """{(xcd, se, sh, cu): rows of that compute unit}, times in us: within a unit from its own s_memtime counter"""
+    hw, xcc = rec[:, 8], rec[:, 9] & 0xf
+    key = (xcc << 8) | (((hw >> 13) & 7) << 5) | (((hw >> 12) & 1) << 4) | ((hw >> 8) & 0xf)
+    out = {}
+    for k in np.unique(key):
+        rows = np.where(key == k)[0]
+        out[int(k)] = rows
+    return out
+
+
+hw = s[:, 8]
+simd = (hw >> 4) & 3
+units = units_of(s)
+r0 = s[:, 10].min()
+print(f"\ndrain per SIMD: {len(units)} compute units by hardware id, {np.mean([len(v) for v in units.values()]):.1f} tiles each "
+      f"(min {min(len(v) for v in units.values())}, max {max(len(v) for v in units.values())})")
+rel = np.arange(-12.0, 0.01, 1.0)
+res_rank, cmp_rank, res_simd = [], [], []
+simd_end, lone, last_begin, tiles_simd = [], [], [], []
+unit_end_rt = []
+for rows in units.values():
+    t0 = s[rows, 0].min()
+    b, l, e = ((s[rows, c] - t0) / tick for c in (0, 1, 2))
+    sd = simd[rows]
+    end = e.max()
+    unit_end_rt.append((s[rows, 11].max() - r0) / 100.0)
+    res = np.array([[((b <= end + t) & (e > end + t) & (sd == q)).sum() for q in range(4)] for t in rel])
+    cmp_ = np.array([[((l <= end + t) & (e > end + t) & (sd == q)).sum() for q in range(4)] for t in rel])
+    res_simd.append(res)
+    res_rank.append(-np.sort(-res, axis=1))
+    cmp_rank.append(-np.sort(-cmp_, axis=1))
+    ends = np.array([e[sd == q].max() if (sd == q).any() else 0.0 for q in range(4)])
+    simd_end.append(np.sort(ends) - end)                # <= 0: how long before the unit's end each SIMD (by rank) went idle
+    tiles_simd.append(np.sort([(sd == q).sum() for q in range(4)]))
+    last_begin.append(end - b.max())
+    # time a SIMD spends with exactly ONE resident wave before its own end (a lone wave runs at the dependent-issue rate)
+    lo = []
+    for q in range(4):
+        bq, eq = np.sort(b[sd == q]), np.sort(e[sd == q])
+        if len(eq) >= 2:
+            lo.append(eq[-1] - max(eq[-2], bq[-1]))
+    lone.append(np.mean(lo) if lo else 0.0)
+res_rank, cmp_rank, res_simd = np.mean(res_rank, axis=0), np.mean(cmp_rank, axis=0), np.mean(res_simd, axis=0)
+print("  waves per SIMD over the last 12 us of a unit (mean over the units; SIMDs of a unit ordered busiest first at each time)")
+print("  t - end   resident: busiest .. idlest      computing: busiest .. idlest      resident by SIMD id 0 .. 3")
+for i, t in enumerate(rel):
+    print(f"  {t:6.1f}    " + " ".join(f"{v:5.2f}" for v in res_rank[i]) + "        " + " ".join(f"{v:5.2f}" for v in cmp_rank[i])
+          + "        " + " ".join(f"{v:5.2f}" for v in res_simd[i]))
+simd_end = np.array(simd_end)
+spread = -simd_end[:, 0]
+print("  end of each SIMD before the end of its unit, us (SIMDs ordered first-idle .. last; median / p90 over the units): "
+      + "  ".join(f"{np.median(simd_end[:, q]):.2f} / {np.percentile(simd_end[:, q], 10):.2f}" for q in range(4)))
+print(f"  spread of the four SIMD end times of a unit: median {np.median(spread):.2f} us, p90 {np.percentile(spread, 90):.2f}, max {spread.max():.2f}; "
+      f"mean idle SIMD time before the unit's end {np.median(-simd_end.mean(axis=1)):.2f} us (median unit)")
+ts = np.array(tiles_simd)
+print(f"  tiles per SIMD of a unit (fewest .. most, mean over the units): " + " ".join(f"{v:.1f}" for v in ts.mean(axis=0)))
+print(f"  last wave of a unit begins {np.median(last_begin):.2f} us before the unit ends (median); a SIMD's final wave is alone on it "
+      f"for {np.median(lone):.2f} us (median unit, mean of its SIMDs; p90 {np.percentile(lone, 90):.2f})")
+ue = np.array(unit_end_rt)
+print(f"  unit end times over the chip (us after the launch's first wave, 100 MHz clock): min {ue.min():.2f}  p10 {np.percentile(ue, 10):.2f}  "
+      f"median {np.median(ue):.2f}  p90 {np.percentile(ue, 90):.2f}  max {ue.max():.2f}   -> last - median {ue.max() - np.median(ue):.2f} us, "
+      f"last - first {ue.max() - ue.min():.2f} us")
+first_begin = np.array([(s[rows, 10].min() - r0) / 100.0 for rows in units.values()])
+print(f"  first wave of a unit begins (us after the launch's first wave): median {np.median(first_begin):.2f}  p90 {np.percentile(first_begin, 90):.2f}  "
+      f"max {first_begin.max():.2f}")
+if both.shape[0] >= 2:
+    s2 = both[1]
+    gap = (s2[:, 10].min() - s[:, 11].max()) / 100.0
+    idle_from_median = (s2[:, 10].min() - r0) / 100.0 - np.median(ue)
+    print(f"  next launch: its first wave begins {gap:.2f} us after this launch's last wave ended (kernel end + dispatch), "
+          f"{idle_from_median:.2f} us after the median unit ended; launch period {(s2[:, 10].min() - r0) / 100.0:.2f} us")
