@@ -122,6 +122,27 @@ __device__ __forceinline__ double ln_table(double u, const double* lntab) {
     return fma((double)ex, 6.93147180559945286227e-01, lntab[2 * k] + p);
 }
 
+// Everything behind the Philox call: the two 53-bit integers (a, b) of a counter -> amp = scale * radius and (cos, sin) of the
+// Box-Muller pair.  Its own routine so that chosen bit patterns can be fed in (tests/host/hip_math_probe.cpp): no seed reaches
+// a = 2^53 - 1 short of a 2^64 search.
+// u1 lies in (0, 1]: a + 0.5 is a tie for a = 2^53 - 1 and rounds to 2^53, u1 == 1, and ln_table(1.0) is exactly +0.0 (f = 1/2,
+// ex = 1: ln c_0 + log1p(r) rounds to -RN(ln 2)).  sqrt_rsqrt(0) is NaN (0 times the infinite seed; measured: both elements of
+// the pair NaN), so the radicand carries a nudge IN the fma that forms it - the smallest denormal, 2^-1074.  -2 lnu is an exact
+// product and >= 4.4e-16 for every other a (a = 2^53 - 2: u1 = 1 - 2^-52), so the sum rounds back to -2 lnu bit for bit: no
+// element of any stream changes but that one pair, whose radius becomes 2.2e-162 (measured; v_rsq_f64 takes denormals) where
+// the definition (oracle/philox_host.py) has 0.  The fma replaces the multiplication and 2^-1074 is the INLINE constant 1 of a
+// 64-bit operand (v_fma_f64 v, v, -2.0, 1): no instruction and no register more (1e-300 cost two VGPRs for the literal).
+__device__ __forceinline__ void box_muller_pair(unsigned long long a, unsigned long long b, double scale, const double* lntab,
+                                                const double* sctab, double& amp, double& cs, double& sn) {
+    const double u1 = ((double)a + 0.5) * 0x1.0p-53;               // (0, 1]
+    const double u2 = ((double)b + 0.5) * 0x1.0p-53;
+    const double lnu = ln_table(u1, lntab);
+    double rad, rinv;
+    rc::sqrt_rsqrt(fma(-2.0, lnu, 0x1.0p-1074), rad, rinv);
+    rc::sincos_table(64.0 * u2, sctab, sn, cs);                    // 64 u2 <= 64: far inside sincos_table's domain
+    amp = scale * rad;
+}
+
 // Box-Muller pair of counter `ctr`: elements 2 ctr = amp * cs and 2 ctr + 1 = amp * sn of stream `seed` (amp = scale * radius).
 // Shared by philox_normal_kernel and by the fidelity kernel that generates its own draws (k_fidelity_philox.inc.h): the two
 // produce the same bits.
@@ -131,13 +152,7 @@ __device__ __forceinline__ void philox_pair(unsigned long long seed, unsigned lo
     philox4x32_10((unsigned int)ctr, (unsigned int)(ctr >> 32), 0u, 0u, (unsigned int)seed, (unsigned int)(seed >> 32), w);
     const unsigned long long a = (((unsigned long long)w[1] << 32) | w[0]) >> 11;
     const unsigned long long b = (((unsigned long long)w[3] << 32) | w[2]) >> 11;
-    const double u1 = ((double)a + 0.5) * 0x1.0p-53;               // (0, 1)
-    const double u2 = ((double)b + 0.5) * 0x1.0p-53;
-    const double lnu = ln_table(u1, lntab);
-    double rad, rinv;
-    rc::sqrt_rsqrt(-2.0 * lnu, rad, rinv);
-    rc::sincos_table(64.0 * u2, sctab, sn, cs);
-    amp = scale * rad;
+    box_muller_pair(a, b, scale, lntab, sctab, amp, cs, sn);
 }
 
 // element `e` of the stream on its own (rare paths only: one Philox call per element)

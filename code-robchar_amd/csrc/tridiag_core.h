@@ -123,7 +123,8 @@ constexpr bool kPolishLargeN = RC_POLISH_LARGE_N;
 constexpr int kFastSweepCap = 10;                // fast path: more sweeps than this for one eigenvalue -> general path
 
 // ---- hardware seeds ---------------------------------------------------------------------------------------
-// v_rsq_f64 / v_rcp_f64 deliver ~5e-8 relative accuracy (measured, scripts/ubench/rsq_acc.hip).  The host build
+// v_rsq_f64 / v_rcp_f64 deliver ~5e-8 relative accuracy (measured, scripts/ubench/rsq_acc.hip; on the 4 000 inputs 10^U(-8, 8)
+// of tests/math_checks.py, against mpmath: 4.97e-8 and 4.17e-8 - the refinements behind them need < 1e-6).  The host build
 // imitates that error (sign taken from a mantissa bit) so that the CPU unit tests exercise the refinement too.
 RC_HD double seed_rsq(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -145,6 +146,10 @@ RC_HD double seed_rcp(double x) {
 // sqrt(x) and 1/sqrt(x) for x > 0 to rounding level: seed y (5e-8), then ONE third-order (Householder) step
 //   e = 1 - x y^2,  y <- y + y e (1/2 + 3/8 e)        (error ~ 5/16 e^3 ~ 3e-22 before rounding)
 // and root = x y.  7 VALU ops in all, no division, no range scaling (operands here are O(1e-300 .. 1e8)).
+// DOMAIN: x in [1e-300, 1e300] (tests/math_checks.py: inverse <= 1.25, root <= 2.25 spacings of the exact value there).  x = 0
+// gives NaN - the seed is infinite and t = 0 * inf - so no caller may pass it: where a radicand can vanish the
+// caller adds a nudge (1e-300 in the fma of the closed-form 2x2 block and of the shift; box_muller_pair adds 2^-1074, which
+// only has to come out finite).
 RC_HD void sqrt_rsqrt(double x, double& root, double& inv) {
     const double y = seed_rsq(x);
     const double t = x * y;
@@ -244,6 +249,11 @@ RC_HD void sincos_reduced(double x, double& s, double& c) {
 // Taylor kernels, truncation 5e-18 / 2e-20), (cos, sin)(n pi/32) from a 64-entry table covering the whole circle -
 // no quadrant logic; the angle-addition formulas combine the two.  19 VALU operations + one 16-byte table read
 // instead of 38.  `tab` = kSinCosTable values: 64 x (cos, sin)(2 pi k / 64), in LDS on the device.
+// DOMAIN (of u = x 32/pi, the argument sincos_table takes): |rint(u)| <= 2^31 - 1, i.e. |x| = |T (lambda_k - lambda_0)| < 2^31 pi/32 =
+// 2.1e8.  The reduction r = u - rint(u) is EXACT, so the accuracy (<= 2 * 2^-53 absolute, tests/math_checks.py) does not decay
+// with |u| inside the domain; beyond it the conversion of n to int saturates and a WRONG TABLE ENTRY is read silently (host
+// build: error 0.47 at u = 2^31 + 5.25).  Every route - fast, rows, ring, csym - shares this limit, so the on-device
+// cross-checks agree with each other there.  (sincos_reduced's own limit is the |x| < ~1e5 stated above it.)
 #define RC_SINCOS_TABLE_VALUES \
     1.0, 0.0, 0.9951847266721969, 0.0980171403295606, \
     0.9807852804032304, 0.19509032201612828, 0.9569403357322088, 0.2902846772544624, \
