@@ -31,6 +31,7 @@ EXPORTS = (
     "rc_mc_fidelity_grad_listed_f64_async", "rc_tail_select_len", "rc_tail_select_f64_async",
     "rc_lbfgs_state_len", "rc_lbfgs_init_f64_async", "rc_lbfgs_advance_f64_async", "rc_lbfgs_result_f64_async",
     "rc_lbfgs_init_box_f64_async", "rc_lbfgs_advance_box_f64_async",
+    "rc_bootstrap_metrics_f64_async", "rc_bootstrap_metrics_f64",
 )
 
 RC_KERNEL_AUTO, RC_KERNEL_TRIDIAG_QL, RC_KERNEL_JACOBI, RC_KERNEL_TRIDIAG_ADJ, RC_KERNEL_EXPM, RC_KERNEL_RING_HH = 0, 1, 2, 3, 4, 5
@@ -172,6 +173,8 @@ def load():
     lib.rc_lbfgs_result_f64_async.argtypes = [i, vp, i, i, ll, dp, dp, dp, dp, vp, vp, vp]
     lib.rc_lbfgs_init_box_f64_async.argtypes = [i, vp, i, i, ll, dp, dp, dp, dp, dp, dp]
     lib.rc_lbfgs_advance_box_f64_async.argtypes = [i, vp, i, i, ll, i, dbl, dp, dp, dp, dp, dbl, dbl, dbl, ll, ll, dp, dp]
+    lib.rc_bootstrap_metrics_f64_async.argtypes = [i, vp, dp, ll, ll, ll, ull, ull, dp, i, ll, ll, i, dp, dp]
+    lib.rc_bootstrap_metrics_f64.argtypes = [i, dp, ll, ll, ll, ull, ull, dp, i, ll, ll, i, dp, dp]
     _lib = lib
     return lib
 

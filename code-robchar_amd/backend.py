@@ -702,6 +702,82 @@ def tail_select(fid, alpha: float, want=TAIL_SELECT_OUTPUTS, device=None):
     return res
 
 
+BOOTSTRAP_OUTPUTS = ("summary", "replicates")
+BOOTSTRAP_ROUTES = {"auto": 0, "lds": 1, "global": 2}
+
+
+def bootstrap_metrics(fid, n_boot: int, seed: int, offset: int = 0, q_thresholds=Q_THRESHOLDS, conf: float = 0.95,
+                      want=BOOTSTRAP_OUTPUTS, route: str = "auto", device=None):
+    """Bootstrap of the per-row metrics of `fid` (C, K), resampled on the GPU (`rc_bootstrap_metrics_f64_async`; the definition
+    is `bootstrap.py`): `n_boot` resamples of every row with replacement from the counter-based stream (`seed`, `offset` in Philox
+    counters; row c of a C-row call equals row 0 of a one-row call at offset + c n_boot ceil(K / 4)).  Dict of the entries named
+    in `want`,
+
+        "replicates" (M, C, B)   every metric of every replicate,
+        "summary"    (M, 4, C)   per metric and row: mean, standard error (ddof = 1; NaN for n_boot = 1), and the lower and upper
+                                 end of the two-sided percentile interval at level `conf` (`bootstrap.ranks`: NumPy's quantile
+                                 methods "lower" and "higher"),
+
+    plus "names": the M = 3 + nq metrics in order, rim1, std, min, q0 ... (signs of `reduce_metrics`: q and min positive).  A row
+    with a NaN gives NaN.  `route`: "auto", "lds" (the row is staged in LDS; K <= 18 432) or "global"; the routes give the same
+    bits.  A float64 torch CUDA tensor in: torch tensors on its device, enqueued on the current stream, no host synchronisation.
+    A NumPy array in: NumPy arrays out (the blocking entry)."""
+    from . import bootstrap as _boot
+    want = tuple(want)
+    if not want or any(w not in BOOTSTRAP_OUTPUTS for w in want):
+        raise ValueError(f"want: a non-empty subset of {BOOTSTRAP_OUTPUTS}, got {want}")
+    if route not in BOOTSTRAP_ROUTES:
+        raise ValueError(f"route: one of {tuple(BOOTSTRAP_ROUTES)}, got {route!r}")
+    if fid.ndim != 2:
+        raise ValueError("fid: expected (C, K)")
+    C, K = (int(v) for v in fid.shape)
+    B = int(n_boot)
+    if K < 1:
+        raise ValueError("fid: K must be positive")
+    if not 1 <= B <= _boot.MAX_N_BOOT:
+        raise ValueError(f"n_boot must be in 1 .. {_boot.MAX_N_BOOT}")
+    seed, offset = int(seed), int(offset)
+    if not (0 <= seed < 2 ** 64 and 0 <= offset < 2 ** 64):
+        raise ValueError("seed and offset must be in 0 .. 2^64 - 1")
+    rank_lo, rank_hi = _boot.ranks(B, conf)
+    thr = np.ascontiguousarray(q_thresholds, dtype=np.float64).reshape(-1)
+    nq = int(thr.size)
+    M = 3 + nq
+    lib = _lib.load()
+    _lib.require_gpu()
+    names = _boot.metric_names(nq)
+    if _is_torch(fid):
+        import torch
+        if not (fid.is_cuda and fid.dtype == torch.float64):
+            raise ValueError("fid must be a float64 CUDA tensor (or a NumPy array)")
+        fid = fid.contiguous()
+        dev = fid.device
+        res = {}
+        if "replicates" in want:
+            res["replicates"] = torch.empty((M, C, B), dtype=torch.float64, device=dev)
+        if "summary" in want:
+            res["summary"] = torch.empty((M, 4, C), dtype=torch.float64, device=dev)
+        ptr = lambda k: ctypes.c_void_p(res[k].data_ptr()) if k in res else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.rc_bootstrap_metrics_f64_async(dev.index or 0, ctypes.c_void_p(stream), ctypes.c_void_p(fid.data_ptr()), C, K, B,
+                                                      seed, offset, _ptr(thr) if nq else None, nq, rank_lo, rank_hi,
+                                                      BOOTSTRAP_ROUTES[route], ptr("replicates"), ptr("summary")))
+        res["names"] = names
+        return res
+    fid = np.ascontiguousarray(fid, dtype=np.float64)
+    res = {}
+    if "replicates" in want:
+        res["replicates"] = np.empty((M, C, B))
+    if "summary" in want:
+        res["summary"] = np.empty((M, 4, C))
+    _lib.check(lib.rc_bootstrap_metrics_f64(device_index(device), _ptr(fid), C, K, B, seed, offset, _ptr(thr) if nq else None, nq,
+                                            rank_lo, rank_hi, BOOTSTRAP_ROUTES[route],
+                                            _ptr(res["replicates"]) if "replicates" in res else None,
+                                            _ptr(res["summary"]) if "summary" in res else None))
+    res["names"] = names
+    return res
+
+
 LBFGS_KINDS = {"raw": 0, "one_minus": 1, "one_minus_plus_std": 2}
 LBFGS_DEFAULTS = {"c1": 1e-4, "gtol": 1e-6, "ftol": 0.0, "maxiter": 100, "maxback": 20}
 

@@ -52,6 +52,7 @@
 #include "csym_core.h"
 #include "sort_core.h"
 #include "select_core.h"
+#include "bootstrap_core.h"
 #include "lbfgs_core.h"
 #include "legacy_rng_core.h"
 #include "mt19937_jump_poly.h"
@@ -106,6 +107,7 @@ typedef __attribute__((address_space(3))) void* rc_lptr_t;
 #include "k_fidelity_dense.inc.h"
 #include "k_reduce_sort.inc.h"
 #include "k_tail_select.inc.h"
+#include "k_bootstrap.inc.h"
 #include "k_lbfgs.inc.h"
 #include "k_draws.inc.h"
 #include "k_fidelity_philox.inc.h"
@@ -1812,6 +1814,78 @@ int rc_tail_select_f64_async(int device, void* stream, const double* fid_dev, lo
         hipLaunchKernelGGL((tail_select_kernel<512, kSelLongU, false>), grid, dim3(512), 0, s, p);
     RC_HIP_CHECK(hipGetLastError());
     return RC_OK;
+}
+
+// ---- bootstrap of the metrics (ABI 15): replicates resampled on the device, summarised through the row sort (k_bootstrap.inc.h) ------
+static void launch_bootstrap(hipStream_t s, const BootParams& p, bool lds) {
+    const dim3 grid((unsigned)(p.C * p.splits)), block(rcboot::kThreads);
+    if (lds && p.nq <= 2)
+        hipLaunchKernelGGL((bootstrap_replicates_kernel<2, true>), grid, block, 0, s, p);
+    else if (lds)
+        hipLaunchKernelGGL((bootstrap_replicates_kernel<rcboot::kMaxQ, true>), grid, block, 0, s, p);
+    else if (p.nq <= 2)
+        hipLaunchKernelGGL((bootstrap_replicates_kernel<2, false>), grid, block, 0, s, p);
+    else
+        hipLaunchKernelGGL((bootstrap_replicates_kernel<rcboot::kMaxQ, false>), grid, block, 0, s, p);
+}
+
+int rc_bootstrap_metrics_f64_async(int device, void* stream, const double* fid_dev, long long C, long long K, long long B,
+                                   unsigned long long seed, unsigned long long offset, const double* q_thresholds, int nq,
+                                   long long rank_lo, long long rank_hi, int route, double* rep_out_dev, double* summary_out_dev) {
+    if (const char* msg = rcboot::check_args(C, K, B, nq, !q_thresholds, rank_lo, rank_hi, route, offset, !fid_dev))
+        return fail(RC_EINVAL, msg);
+    if (C == 0 || (!rep_out_dev && !summary_out_dev)) return RC_OK;
+    RC_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    const long long R = (rcboot::kFixedMetrics + nq) * C;          // replicate rows: (metric, c)
+    // workspace of THIS call, allocated and released in stream order: the replicates when the caller does not want them, and
+    // the sorted rows of the summary
+    StreamFree rep_ws{nullptr, s}, sorted_ws{nullptr, s};
+    double* rep = rep_out_dev;
+    if (!rep) {
+        RC_HIP_CHECK(hipMallocAsync(&rep_ws.p, (size_t)R * B * sizeof(double), s));
+        rep = (double*)rep_ws.p;
+    }
+    BootParams p{};
+    p.fid = fid_dev;
+    p.C = C;
+    p.K = K;
+    p.B = B;
+    p.seed = seed;
+    p.offset = offset;
+    p.nq = nq;
+    p.splits = rcboot::choose_splits(C, B);
+    for (int j = 0; j < rcboot::kMaxQ; ++j) p.thr[j] = j < nq ? q_thresholds[j] : __builtin_inf();
+    p.rep = rep;
+    launch_bootstrap(s, p, route == 1 || (route == 0 && K <= rcboot::kLdsMaxK));
+    RC_HIP_CHECK(hipGetLastError());                               // (the LDS route declares 144 KiB of static LDS: a refused launch shows here)
+    if (!summary_out_dev) return RC_OK;
+    RC_HIP_CHECK(hipMallocAsync(&sorted_ws.p, (size_t)R * B * sizeof(double), s));
+    if (int rc = enqueue_reduce(s, rep, R, B, nullptr, 0, 0.0, nullptr, nullptr, nullptr, nullptr, (double*)sorted_ws.p)) return rc;
+    hipLaunchKernelGGL(bootstrap_summary_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, s, rep, (const double*)sorted_ws.p, R, C, B,
+                       rank_lo, rank_hi, summary_out_dev);
+    RC_HIP_CHECK(hipGetLastError());
+    return RC_OK;
+}
+
+int rc_bootstrap_metrics_f64(int device, const double* fid, long long C, long long K, long long B, unsigned long long seed,
+                             unsigned long long offset, const double* q_thresholds, int nq, long long rank_lo, long long rank_hi,
+                             int route, double* rep_out, double* summary_out) {
+    if (const char* msg = rcboot::check_args(C, K, B, nq, !q_thresholds, rank_lo, rank_hi, route, offset, !fid))
+        return fail(RC_EINVAL, msg);
+    if (C == 0 || (!rep_out && !summary_out)) return RC_OK;
+    if (int rc = device_in_range(device)) return rc;
+    std::lock_guard<std::mutex> lk(g_ctx[device].mu);
+    Staging ws;
+    if (int rc = get_ctx(device, &ws.ctx)) return rc;
+    const size_t M = (size_t)(rcboot::kFixedMetrics + nq);
+    const int s_fid = ws.in(fid, (size_t)C * K * sizeof(double)), s_rep = ws.out(rep_out, M * C * B * sizeof(double)),
+              s_sum = ws.out(summary_out, M * rcboot::kSummaryFields * C * sizeof(double), true);
+    if (int rc = ws.stage_in()) return rc;
+    if (int rc = rc_bootstrap_metrics_f64_async(device, ws.ctx->stream, ws.ptr(s_fid), C, K, B, seed, offset, q_thresholds, nq, rank_lo,
+                                                rank_hi, route, ws.ptr(s_rep), ws.ptr(s_sum)))
+        return rc;
+    return ws.stage_out();
 }
 
 // ---- batched L-BFGS (ABI 13): the state machine of lbfgs.py, one lane per row (k_lbfgs.inc.h) ----------------------------------

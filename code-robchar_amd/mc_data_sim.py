@@ -743,6 +743,87 @@ class MCDataSim:
                 direction[j0:j1, :nvalid] = res["direction"].reshape(j1 - j0, nvalid, N, 3)
         return {"noises": noises.tolist(), "fav": fav.tolist(), "dfav_dlogsigma": slope.tolist(), "direction": direction.tolist()}
 
+    # ------------------------------------------------------------------ bootstrap error bars of the metrics
+    def get_bootstrap_dict(self, training_noise: str = None, noises: np.ndarray = None, algoname=None, n_boot: int = 1000,
+                           conf: float = 0.95, seed: int = None) -> dict:
+        """Bootstrap error bars of the five `.mcm` metrics, per algorithm, sigma level and controller:
+
+            {algo: {metric: {"se": [L][C], "lower": [L][C], "upper": [L][C]}}}     (nested lists, metric in METRIC_NAMES)
+
+        `se` is the standard error of the metric over `n_boot` resamples (with replacement) of the controller's K fidelities at
+        the level, `lower` / `upper` the two-sided percentile interval at level `conf` - in the reference's sign convention: Q and
+        worst case are stored negated, so their lower is minus the upper end of the positive quantity.  Controllers padded up to
+        `numcontrollers` are NaN.  The bootstrap of a minimum (worst case) is NOT a consistent estimator: its row is reported for
+        table completeness, not as an error bar to rely on.
+
+        The fidelities are those of `get_fid_dists` (computed there if no cache file has them): the `DeviceFids` handle where the
+        tensor is on the GPU, uploaded otherwise.  They are resampled on the device (`backend.bootstrap_metrics`), per algorithm
+        ONE launch over the L * C rows, row index j C + c, from the counter-based stream `seed` (default: the instance's) at
+        offset 0 for EVERY algorithm.  Neither NumPy's global stream nor the instance's Philox offset is consumed by the
+        resampling: a later `get_fid_dists` is unaffected.
+
+        Cached as JSON in `get_mcname(...) + "b"` together with `n_boot`, `conf` and `seed`; the file is reused only when all
+        three match (and not written with cache_format="none").  One GPU: raises NotImplementedError under an initialised process
+        group or with `devices=...`."""
+        if self.devices is not None:
+            raise NotImplementedError("get_bootstrap_dict runs on one GPU (devices=... is not supported)")
+        try:
+            import torch.distributed as dist
+            grouped = dist.is_available() and dist.is_initialized()
+        except ImportError:
+            grouped = False
+        if grouped:
+            raise NotImplementedError("get_bootstrap_dict runs on one GPU (not under an initialised process group)")
+        if isinstance(algoname, str):
+            algos = [algoname]
+        elif algoname is None:
+            algos = list(self.algos)
+        else:
+            algos = list(algoname)
+        if noises is None:
+            noises = self.noises
+        if training_noise is None:
+            training_noise = self.training_noise
+        noises = np.asarray(noises)
+        n_boot, conf = int(n_boot), float(conf)
+        seed = int(self.seed if seed is None else seed)
+        path = self.get_mcname(training_noise, noises) + "b"
+        table = {}
+        if os.path.exists(path):
+            with open(path, "rb") as fh:
+                cached = json.load(fh)
+            if isinstance(cached, dict) and cached.get("n_boot") == n_boot and cached.get("conf") == conf and cached.get("seed") == seed:
+                table = cached.get("bootstrap", {})
+        missing = [a for a in algos if a not in table]
+        if missing:
+            dists = self.get_fid_dists(training_noise, noises, algoname if isinstance(algoname, str) else None)
+            for name in missing:
+                table[name] = self._bootstrap_of_algo(dists[name], n_boot, conf, seed)
+            if self.cache_format != "none":
+                with open(path, "w") as fh:
+                    json.dump({"n_boot": n_boot, "conf": conf, "seed": seed, "bootstrap": table}, fh)
+        return {name: table[name] for name in algos}
+
+    def _bootstrap_of_algo(self, dists, n_boot: int, conf: float, seed: int) -> dict:
+        """One algorithm of `get_bootstrap_dict`: the (L, C, K) tensor as L * C rows through one launch."""
+        import torch
+        dev = backend.compute_device()
+        if isinstance(dists, DeviceFids) and dists.tensor is not None:
+            L, C, K = dists.shape
+            rows = dists.tensor
+            if int(rows.shape[1]) < C:                   # the padded controllers: NaN rows, so that row j C + c is (level j, controller c)
+                full = torch.full((L, C, K), float("nan"), dtype=torch.float64, device=rows.device)
+                full[:, :int(rows.shape[1])] = rows
+                rows = full
+        else:
+            T = np.ascontiguousarray(np.asarray(dists, dtype=np.float64))
+            L, C, K = T.shape
+            rows = torch.from_numpy(T).to(dev)
+        res = backend.bootstrap_metrics(rows.reshape(L * C, K), n_boot, seed, offset=0, q_thresholds=backend.Q_THRESHOLDS, conf=conf,
+                                        want=("summary",))
+        named = rim_metrics.bootstrap_named(res["summary"].cpu().numpy())
+        return {metric: {k: v.reshape(L, C).tolist() for k, v in tab.items()} for metric, tab in named.items()}
+
     # ------------------------------------------------------------------ second caller of the kernel
     _RIMS_CHUNK_DRAWS = 1 << 27          # host draws per batch (1 GiB of fp64)
 

@@ -171,6 +171,37 @@ def wd_from_ideal_fids(fids):
     return _lazy_row_metric(fids, lambda red: np.asarray(red["rim1"])[0], sort_in_place=True)
 
 
+def bootstrap_named(summary) -> dict:
+    """{metric name: {"se", "lower", "upper"}} of the five `.mcm` metrics from a `backend.bootstrap_metrics` summary (5, 4, C)
+    taken with `backend.Q_THRESHOLDS`, in the reference's sign convention: Q and worst case are stored negated, so their interval
+    is mirrored (lower = -upper of the positive quantity); a standard error has no sign."""
+    s = np.asarray(summary)
+    if s.shape[:2] != (5, 4):
+        raise ValueError("summary: expected (5, 4, C) - rim1, std, min and the two Q thresholds")
+    out = {}
+    for name, row, negated in ((METRIC_NAMES[0], 0, False), (METRIC_NAMES[1], 3, True), (METRIC_NAMES[2], 4, True),
+                               (METRIC_NAMES[3], 1, False), (METRIC_NAMES[4], 2, True)):
+        lower, upper = (-s[row, 3], -s[row, 2]) if negated else (s[row, 2], s[row, 3])
+        out[name] = {"se": s[row, 1], "lower": lower, "upper": upper}
+    return out
+
+
+def bootstrap_metrics(fids, n_boot: int = 1000, seed: int = 0, conf: float = 0.95, offset: int = 0, device=None) -> dict:
+    """Bootstrap error bars of the five `.mcm` metrics of a sample (1-D) or of every row of a (C, K) table, resampled on the GPU
+    (`backend.bootstrap_metrics`): {metric name: {"se", "lower", "upper"}}, floats for a 1-D sample and (C,) arrays for rows -
+    the standard error over `n_boot` resamples and the two-sided percentile interval at level `conf`, in the signs of
+    `metric_table` (see `bootstrap_named`).  The bootstrap of a minimum (worst case) is not a consistent estimator; it is
+    reported for table completeness."""
+    arr = _as_fids(fids)
+    vector = arr.ndim == 1
+    res = backend.bootstrap_metrics(np.ascontiguousarray(arr.reshape(1, -1) if vector else arr, dtype=np.float64), n_boot, seed,
+                                    offset=offset, q_thresholds=backend.Q_THRESHOLDS, conf=conf, want=("summary",), device=device)
+    named = bootstrap_named(res["summary"])
+    if vector:
+        return {name: {k: float(v[0]) for k, v in tab.items()} for name, tab in named.items()}
+    return named
+
+
 @dataclass
 class Q_partial:
     """mcsim.py:169-176: Q_fids with the threshold bound at construction."""

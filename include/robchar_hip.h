@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 14      /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 15     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -66,7 +66,8 @@ extern "C" {
                                   12: + rc_tail_select_len, rc_tail_select_f64_async (additive);
                                   13: + rc_lbfgs_state_len, rc_lbfgs_init_f64_async, rc_lbfgs_advance_f64_async,
                                       rc_lbfgs_result_f64_async (additive);
-                                  14: + rc_lbfgs_init_box_f64_async, rc_lbfgs_advance_box_f64_async (additive) */
+                                  14: + rc_lbfgs_init_box_f64_async, rc_lbfgs_advance_box_f64_async (additive);
+                                  15: + rc_bootstrap_metrics_f64_async, rc_bootstrap_metrics_f64 (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -411,6 +412,39 @@ int rc_lbfgs_advance_box_f64_async(int device, void* stream, int ndim, int m, lo
                                    const double* row_a_dev, const double* row_b_dev, const double* lo_dev, const double* hi_dev,
                                    double c1, double gtol, double ftol, long long maxiter, long long maxback,
                                    double* state_dev, double* trial_dev);
+
+/* (ABI 15) Bootstrap of the per-controller metrics, resampled on the device: B replicates of every row of fid [C][K], each a
+ * resample of the row's K values with replacement, and their summary - a per-metric error bar from the samples already there.
+ * The definition is code-robchar_amd/bootstrap.py (NumPy).
+ * Index stream: Philox4x32-10 as in rc_draws_philox_f64_async, key = seed, counter high words 0.  With Q = ceil(K / 4), draw t
+ * (0 <= t < K) of replicate b of row c is output word (t & 3) of counter   offset + (c B + b) Q + (t >> 2),   and
+ *     idx = (word * K) >> 32.
+ * No rejection step: the bias, below K / 2^32, is part of the definition.  Row c of a C-row call equals row 0 of a one-row call
+ * with offset + c B Q.
+ * With m = the row's mean (fixed summation order), f the K gathered values and g = f - m:   S1 = sum g,  S2 = sum g^2,
+ *     rim1 = 1 - (m + S1 / K),   std = sqrt(max(0, S2 / K - (S1 / K)^2))  (population),   min = min f,
+ *     q[i] = #{f >= q_thresholds[i]} / K        (signs of rc_reduce_f64: q and min positive).
+ * A row holding any NaN gives NaN in every output.  One wave owns one replicate and its summation order depends on K alone: same
+ * inputs, same bits, on either route and however the replicates are spread over workgroups.  No atomics.
+ *     rep_out     [M][C][B], M = 3 + nq in the order rim1, std, min, q[0 .. nq)         optional (NULL = not wanted)
+ *     summary_out [M][4][C]: over the B replicates of a metric and row, their mean, their standard error (std with ddof = 1;
+ *                 NaN for B = 1) and the order statistics of ranks rank_lo and rank_hi (0-based, ascending)        optional
+ * For a two-sided interval at level conf take a = (1 - conf) / 2, rank_lo = floor(a (B - 1)), rank_hi = ceil((1 - a) (B - 1)).
+ * route: 0 = by K, 1 = the row is staged once per workgroup into LDS and resampled from there (K <= 18432: 144 KiB of a CU's
+ * 160 KiB), 2 = gathered from global memory (any K).  The routes give the same bits.
+ * Argument checks before any HIP call, RC_EINVAL with a message: C negative; K < 1 or above 2^31 - 1; B < 1 or above 16384 (the
+ * row sort behind the summary); nq outside [0, 8], or q_thresholds NULL with nq > 0; ranks outside 0 <= rank_lo <= rank_hi < B;
+ * route outside 0 .. 2, or route 1 with K above 18432; offset + C B Q wrapping 2^64; fid NULL with C > 0.  C = 0: RC_OK, nothing
+ * written.
+ * _async: enqueue-only on `stream`, device pointers (q_thresholds is a HOST array, read before the call returns); its workspace
+ * (the sorted replicates, and the replicates when rep_out is NULL) is allocated and released in stream order.  The blocking
+ * entry takes host or device arrays. */
+int rc_bootstrap_metrics_f64_async(int device, void* stream, const double* fid_dev, long long C, long long K, long long B,
+                                   unsigned long long seed, unsigned long long offset, const double* q_thresholds, int nq,
+                                   long long rank_lo, long long rank_hi, int route, double* rep_out_dev, double* summary_out_dev);
+int rc_bootstrap_metrics_f64(int device, const double* fid, long long C, long long K, long long B, unsigned long long seed,
+                             unsigned long long offset, const double* q_thresholds, int nq, long long rank_lo, long long rank_hi,
+                             int route, double* rep_out, double* summary_out);
 
 /* (ABI 6) 1 when the kernel above is the faster of the two bit-identical routes for this geometry (N <= 13, or N = 14 with
  * {in, out} = {0, N-1}), else 0; 0 everywhere when ROBCHAR_PHILOX_FUSED=0 is in the environment (read per call).  The ONE
