@@ -32,6 +32,8 @@ EXPORTS = (
     "rc_lbfgs_state_len", "rc_lbfgs_init_f64_async", "rc_lbfgs_advance_f64_async", "rc_lbfgs_result_f64_async",
     "rc_lbfgs_init_box_f64_async", "rc_lbfgs_advance_box_f64_async",
     "rc_bootstrap_metrics_f64_async", "rc_bootstrap_metrics_f64",
+    "rc_mc_fidelity_times_f64_async", "rc_mc_fidelity_times_f64", "rc_mc_fidelity_times_philox_f64_async",
+    "rc_stats_times_general_tiles",
 )
 
 RC_KERNEL_AUTO, RC_KERNEL_TRIDIAG_QL, RC_KERNEL_JACOBI, RC_KERNEL_TRIDIAG_ADJ, RC_KERNEL_EXPM, RC_KERNEL_RING_HH = 0, 1, 2, 3, 4, 5
@@ -175,6 +177,11 @@ def load():
     lib.rc_lbfgs_advance_box_f64_async.argtypes = [i, vp, i, i, ll, i, dbl, dp, dp, dp, dp, dbl, dbl, dbl, ll, ll, dp, dp]
     lib.rc_bootstrap_metrics_f64_async.argtypes = [i, vp, dp, ll, ll, ll, ull, ull, dp, i, ll, ll, i, dp, dp]
     lib.rc_bootstrap_metrics_f64.argtypes = [i, dp, ll, ll, ll, ull, ull, dp, i, ll, ll, i, dp, dp]
+    lib.rc_mc_fidelity_times_f64_async.argtypes = [i, vp, i, i, i, dp, dp, i, dp, dp, ll, ll, ll, i, dp, dp, dp, dp, dp, dp]
+    lib.rc_mc_fidelity_times_f64.argtypes = [i, i, i, i, dp, dp, i, dp, dp, ll, ll, ll, i, dp, dp, dp, dp, dp, dp]
+    lib.rc_mc_fidelity_times_philox_f64_async.argtypes = [i, vp, i, i, i, dp, dp, i, dp, ull, ull, dbl, dp, ll, ll, i, dp, dp, dp, dp, dp, dp]
+    lib.rc_stats_times_general_tiles.argtypes = [i, i]
+    lib.rc_stats_times_general_tiles.restype = ll
     _lib = lib
     return lib
 

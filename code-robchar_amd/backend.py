@@ -261,6 +261,182 @@ def sens_general_tiles(device=None, reset: bool = False) -> int:
     return _tile_counter("rc_stats_sens_general_tiles", device, reset)
 
 
+TIMES_OUTPUTS = ("fid", "wsum", "min")
+MAX_TIMES = 64                       # RC_MAX_TIMES of include/robchar_hip.h
+MAX_NSPIN_TIMES = 16                 # RC_MAX_NSPIN_FAST
+
+
+def readout_times(T, tscale=None, tshift=None):
+    """The (C, M) readout times t_cj = |T_c tscale_j + tshift_j| the readout-time kernels evaluate: NumPy's product, then sum,
+    then absolute value - the kernels' own rounding, bit for bit.  `T`: the controllers' time entries as stored (signed); an
+    absent array is all 1 / all 0; with both absent M = 1."""
+    T = np.asarray(T, dtype=np.float64).reshape(-1)
+    a, b, _ = _times_grid(tscale, tshift, None)
+    return np.abs(T[:, None] * a[None, :] + b[None, :])
+
+
+def _times_grid(tscale, tshift, weights):
+    """(tscale, tshift, weights) as float64 NumPy vectors of one length M in 1 .. MAX_TIMES; an absent scale / shift is filled
+    with 1 / 0, absent weights stay None."""
+    vec = lambda v: None if v is None else np.ascontiguousarray(
+        v.detach().cpu().numpy() if _is_torch(v) else v, dtype=np.float64).reshape(-1)
+    a, b, w = vec(tscale), vec(tshift), vec(weights)
+    lens = {len(v) for v in (a, b, w) if v is not None}
+    if len(lens) > 1:
+        raise ValueError(f"tscale, tshift and weights must have one length, got {sorted(lens)}")
+    M = lens.pop() if lens else 1
+    if not (1 <= M <= MAX_TIMES):
+        raise ValueError(f"the grid must hold 1 .. {MAX_TIMES} times, got {M}")
+    return (np.ones(M) if a is None else a), (np.zeros(M) if b is None else b), w
+
+
+_TIMES_GRIDS = {}                   # (device, grid bytes) -> (3, M) device tensor: tscale, tshift, weights (zeros when absent)
+
+
+def _times_grid_on_device(a, b, w, dev):
+    """The grid as one (3, M) tensor on `dev`, uploaded once per distinct grid (a blocking copy: it has landed when this returns,
+    so the tensor may be read from any stream) and kept - a caller that sweeps controllers over one grid pays no copy per call."""
+    import torch
+    key = (str(dev), a.tobytes(), b.tobytes(), None if w is None else w.tobytes())
+    grid = _TIMES_GRIDS.get(key)
+    if grid is None:
+        if len(_TIMES_GRIDS) >= 16:
+            _TIMES_GRIDS.clear()
+        grid = torch.from_numpy(np.stack([a, b, w if w is not None else np.zeros(len(a))])).to(dev)
+        _TIMES_GRIDS[key] = grid
+    return grid
+
+
+def _times_want(want, weights, nspin, inspin, outspin):
+    _check_geometry(nspin, inspin, outspin)
+    if nspin > MAX_NSPIN_TIMES:
+        raise ValueError(f"the readout-time kernels support chains of N <= {MAX_NSPIN_TIMES} spins")
+    want = tuple(want)
+    if not want or any(w not in TIMES_OUTPUTS for w in want):
+        raise ValueError(f"want: a non-empty subset of {TIMES_OUTPUTS}, got {want}")
+    if "wsum" in want and weights is None:
+        raise ValueError("want 'wsum' needs weights")
+    return want
+
+
+def mc_fidelity_times(controllers, draws, nspin: int, inspin: int, outspin: int, tscale=None, tshift=None, weights=None,
+                      want=("fid",), h0_diag=None, h0_offdiag=None, device=None):
+    """Fidelities on a grid of M readout times from ONE eigen decomposition per sample (`rc_mc_fidelity_times_f64[_async]`; chain
+    topology, N <= 16, any (in, out)): F_j(c, k) = |<out| exp(-i H_ck t_cj) |in>|^2 at t_cj = `readout_times(T, tscale, tshift)`.
+    Returns a dict with the entries named in `want`:
+
+        "fid"  (M, C, K)   M slabs, each what `mc_fidelity(kernel="tridiag_ql")` gives for controllers whose time entry is t_cj,
+                           bit for bit: `reduce_metrics`, `bootstrap_metrics`, `tail_select` take slab j unchanged
+        "wsum" (C, K)      acc = weights[0] F_0; acc = fma(weights[j], F_j, acc) in the order of j (needs `weights`)
+        "min"  (C, K)      min_j F_j
+
+    `tscale`, `tshift`, `weights`: (M,) arrays, 1 <= M <= 64; an absent scale / shift is all 1 / all 0.  Shapes and the
+    NumPy / torch convention as in `mc_fidelity`: NumPy in -> NumPy out (blocking); torch CUDA draws -> tensors on the same device,
+    enqueued on the current stream; draws of shape (1, K, N, 3) with C > 1 = ONE draw set for every controller.  A NaN controller
+    row gives NaN in every output."""
+    want = _times_want(want, weights, nspin, inspin, outspin)
+    a, b, w = _times_grid(tscale, tshift, weights)
+    M = len(a)
+    h0d = _small(h0_diag, nspin, "h0_diag")
+    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
+    C = int(controllers.shape[0]) if hasattr(controllers, "shape") else len(controllers)
+    if not hasattr(draws, "shape"):
+        draws = np.asarray(draws, dtype=np.float64)
+    shared = int(draws.shape[0]) == 1 and C > 1
+    K = int(draws.shape[1])
+    if tuple(draws.shape) != ((1 if shared else C), K, nspin, 3):
+        raise ValueError(f"draws: expected ({C}, K, {nspin}, 3) or (1, K, {nspin}, 3), got {tuple(draws.shape)}")
+    stride = 0 if shared else K * nspin * 3
+    shapes = {"fid": (M, C, K), "wsum": (C, K), "min": (C, K)}
+    lib = _lib.load()
+    _lib.require_gpu()
+    device = device_index(device)
+    if shared and not _is_torch(draws):              # (the shared form through the enqueue path, as in `mc_fidelity`)
+        import torch
+        dev_t = torch.device("cuda", device)
+        res_t = mc_fidelity_times(torch.as_tensor(np.ascontiguousarray(controllers, dtype=np.float64)).to(dev_t),
+                                  torch.as_tensor(np.ascontiguousarray(draws, dtype=np.float64)).to(dev_t), nspin, inspin, outspin,
+                                  tscale=a, tshift=b, weights=w, want=want, h0_diag=h0_diag, h0_offdiag=h0_offdiag)
+        return {k: v.cpu().numpy() for k, v in res_t.items()}
+    if _is_torch(draws):
+        import torch
+        if not (draws.is_cuda and draws.dtype == torch.float64 and draws.is_contiguous()):
+            raise ValueError("draws must be a contiguous float64 CUDA tensor")
+        dev = draws.device
+        ctrl = controllers if _is_torch(controllers) else torch.as_tensor(np.asarray(controllers, dtype=np.float64))
+        ctrl = ctrl.to(device=dev, dtype=torch.float64).contiguous()
+        if tuple(ctrl.shape) != (C, nspin + 1):
+            raise ValueError(f"controllers: expected ({C}, {nspin + 1}), got {tuple(ctrl.shape)}")
+        grid = _times_grid_on_device(a, b, w, dev)
+        res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
+        ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in TIMES_OUTPUTS]
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.rc_mc_fidelity_times_f64_async(
+            dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), 0, ctypes.c_void_p(ctrl.data_ptr()),
+            ctypes.c_void_p(draws.data_ptr()), stride, C, K, M, ctypes.c_void_p(grid[0].data_ptr()),
+            ctypes.c_void_p(grid[1].data_ptr()), ctypes.c_void_p(grid[2].data_ptr()) if w is not None else None, *ptr))
+        return res
+    draws = np.ascontiguousarray(draws, dtype=np.float64)
+    ctrl = _np_f64(controllers, (C, nspin + 1), "controllers")
+    res = {k: np.empty(shapes[k], dtype=np.float64) for k in want}
+    _lib.check(lib.rc_mc_fidelity_times_f64(device, nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), 0, _ptr(ctrl), _ptr(draws), stride, C,
+                                            K, M, _ptr(a), _ptr(b), _ptr(w), *[_ptr(res.get(k)) for k in TIMES_OUTPUTS]))
+    return res
+
+
+def mc_fidelity_times_philox(controllers, n_draws: int, nspin: int, inspin: int, outspin: int, seed: int, offset: int = 0,
+                             sigma=0.05, tscale=None, tshift=None, weights=None, want=("fid",), h0_diag=None, h0_offdiag=None):
+    """`mc_fidelity_times` with the counter-based draws generated INSIDE the kernel (`rc_mc_fidelity_times_philox_f64_async`):
+    controllers (C, N+1) torch CUDA tensor (a NumPy array is uploaded to the current device) -> dict of torch tensors on that
+    device, the entries named in `want`, enqueued on the current stream; bit-identical to
+    `mc_fidelity_times(controllers, philox_normal((C, K, N, 3), seed, scale=sigma, offset=offset), ...)` without that tensor.
+    `sigma`: a float, or a (C,) tensor / array (one scale per controller row: every sigma level of an algorithm in one launch)."""
+    import torch
+    want = _times_want(want, weights, nspin, inspin, outspin)
+    a, b, w = _times_grid(tscale, tshift, weights)
+    M = len(a)
+    if not _is_torch(controllers):
+        controllers = np.ascontiguousarray(controllers, dtype=np.float64)
+    if controllers.ndim != 2 or int(controllers.shape[1]) != nspin + 1:
+        raise ValueError(f"controllers: expected (C, {nspin + 1}), got {tuple(controllers.shape)}")
+    C, K = int(controllers.shape[0]), int(n_draws)
+    if K < 0:
+        raise ValueError("n_draws must be non-negative")
+    if not _is_torch(sigma) and np.ndim(sigma) > 0:
+        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+    if np.ndim(sigma) > 0 and tuple(sigma.shape) != (C,):
+        raise ValueError("sigma: a float or a (C,) tensor")
+    h0d = _small(h0_diag, nspin, "h0_diag")
+    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
+    lib = _lib.load()
+    _lib.require_gpu()
+    if not _is_torch(controllers):
+        controllers = torch.from_numpy(controllers).to(compute_device())
+    if not controllers.is_cuda:
+        raise ValueError("controllers must be a torch CUDA tensor (or a NumPy array, which is uploaded)")
+    dev = controllers.device
+    ctrl = controllers.to(dtype=torch.float64).contiguous()
+    rows = None
+    if np.ndim(sigma) > 0:
+        rows = (sigma if _is_torch(sigma) else torch.from_numpy(sigma)).to(device=dev, dtype=torch.float64).contiguous()
+    grid = _times_grid_on_device(a, b, w, dev)
+    shapes = {"fid": (M, C, K), "wsum": (C, K), "min": (C, K)}
+    res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
+    ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in TIMES_OUTPUTS]
+    stream = torch.cuda.current_stream(dev).cuda_stream
+    _lib.check(lib.rc_mc_fidelity_times_philox_f64_async(
+        dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), 0, ctypes.c_void_p(ctrl.data_ptr()),
+        int(seed) & (2 ** 64 - 1), int(offset), 0.0 if rows is not None else float(sigma),
+        ctypes.c_void_p(rows.data_ptr()) if rows is not None else None, C, K, M, ctypes.c_void_p(grid[0].data_ptr()),
+        ctypes.c_void_p(grid[1].data_ptr()), ctypes.c_void_p(grid[2].data_ptr()) if w is not None else None, *ptr))
+    return res
+
+
+def times_general_tiles(device=None, reset: bool = False) -> int:
+    """Tiles of the readout-time kernels in which some sample took the textbook per-sample QL since the last reset (diagnostic)."""
+    return _tile_counter("rc_stats_times_general_tiles", device, reset)
+
+
 def reduce_metrics(fid, q_thresholds=Q_THRESHOLDS, dkw_eps: float = 0.0, want_sorted: bool = False,
                    device=None, out=None, overlapped: bool = True):
     """Per-controller reductions of a (C, K) fidelity slab on the GPU.

@@ -138,4 +138,30 @@ struct GradListedParams {
     StaticH h0;
 };
 
+// fidelity on a grid of M readout times (k_fidelity_times.inc.h): FidParams' geometry, t_cj = |T_c tscale_j + tshift_j|, three
+// optional outputs.  mc_fid_times_kernel reads `draws`; mc_fid_times_philox_kernel generates sample (c, k), site i, slot s as
+// element  offset + ((c K + k) N + i) 3 + s  of stream `seed` and ignores `draws`, `draw_cstride` and `align16`.
+struct TimesParams {
+    const double* ctrl;    // [C][N+1]
+    const double* draws;   // [C][K][N][3]
+    double* fid;           // [M][C][K] or NULL
+    double* wsum;          // [C][K] or NULL (needs `weights`)
+    double* fmin;          // [C][K] or NULL
+    const double* tscale;  // [M] or NULL: 1
+    const double* tshift;  // [M] or NULL: 0
+    const double* weights; // [M] or NULL
+    int M;
+    long long C, K;
+    long long draw_cstride;     // elements between consecutive controllers' draw blocks (K*3N; 0 = shared set)
+    long long tiles_per_ctrl;   // ceil(K / 64)
+    long long ntiles;           // C * tiles_per_ctrl
+    int in, out;
+    int align16;
+    unsigned long long seed;
+    unsigned long long offset;        // stream element of sample (c = 0, k = 0), site 0, slot 0
+    const double* sigma_rows;         // [C] scale per controller row, or NULL: `sigma` for all
+    double sigma;
+    StaticH h0;
+};
+
 }  // namespace rckp

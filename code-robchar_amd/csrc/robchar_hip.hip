@@ -75,6 +75,10 @@ __attribute__((visibility("hidden"))) int rc_grad_counter_addr(void** addr);
 __attribute__((visibility("hidden"))) int rc_sens_launch(int N, void* stream, const rckp::SensParams* p, double* mean);
 __attribute__((visibility("hidden"))) int rc_sens_counter_addr(void** addr);
 __attribute__((visibility("hidden"))) int rc_sens_philox_launch(int N, void* stream, const rckp::SensPhiloxParams* p, double* mean);
+// fourth translation unit (robchar_times.hip): the fidelity on a grid of readout times
+__attribute__((visibility("hidden"))) int rc_times_launch(int N, void* stream, const rckp::TimesParams* p);
+__attribute__((visibility("hidden"))) int rc_times_philox_launch(int N, void* stream, const rckp::TimesParams* p);
+__attribute__((visibility("hidden"))) int rc_times_counter_addr(void** addr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1679,6 +1683,139 @@ int rc_mc_fidelity_sens_f64(int device, int N, int in, int out, const double* h0
 
 long long rc_stats_sens_general_tiles(int device, int reset) {
     return read_tile_counter(device, reset, rc_sens_counter_addr, "reading the sensitivity kernel's tile counter failed");
+}
+
+// ------------------------------------------------------------------------------------------------
+// fidelity on a grid of readout times (robchar_times.hip)
+// ------------------------------------------------------------------------------------------------
+// Argument checks of the three entries - all before any HIP call.  `stride` set: the entry takes a draw tensor (its default is
+// filled in); NULL: it generates its draws from `sigma` / `sigma_rows`.  *empty: nothing to do (RC_OK).
+static int check_times_args(int N, int in, int out, int ring, const void* ctrl, const void* draws, long long* stride, double sigma,
+                            const void* sigma_rows, long long C, long long K, int M, const void* weights, const void* fid,
+                            const void* wsum, const void* fmin, bool* empty) {
+    *empty = false;
+    if (int rc = check_common(N, in, out, C, K)) return rc;
+    if (N > RC_MAX_NSPIN_FAST)
+        return fail(RC_ENOSUP, "the readout-time kernels support chains of N <= " + std::to_string(RC_MAX_NSPIN_FAST) + " spins");
+    if (ring) return fail(RC_ENOSUP, "the readout-time kernels support the chain topology only");
+    if (M < 1 || M > RC_MAX_TIMES) return fail(RC_EINVAL, "M must be in [1, " + std::to_string(RC_MAX_TIMES) + "]");
+    if (!fid && !wsum && !fmin) return fail(RC_EINVAL, "no output requested (fid_out, wsum_out and fmin_out are all NULL)");
+    if (wsum && !weights) return fail(RC_EINVAL, "wsum_out needs weights");
+    if (stride && *stride < 0) *stride = K * N * 3;
+    if (stride && *stride != 0 && *stride < K * N * 3) return fail(RC_EINVAL, "draws_ctrl_stride overlaps controllers");
+    if (!stride && !sigma_rows && !(sigma >= 0.0 && sigma < HUGE_VAL))
+        return fail(RC_EINVAL, "sigma must be finite and non-negative (or give sigma_rows)");
+    if (C == 0 || K == 0) {
+        *empty = true;
+        return RC_OK;
+    }
+    if (!ctrl || (stride && !draws)) return fail(RC_EINVAL, "NULL array pointer");
+    if ((C * ((K + 63) / 64)) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    return RC_OK;
+}
+
+// what the two kernels' parameter blocks have in common; device pointers, checked arguments
+static void fill_times_params(rckp::TimesParams& p, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
+                              const double* ctrl, long long C, long long K, int M, const double* tscale, const double* tshift,
+                              const double* weights, double* fid, double* wsum, double* fmin) {
+    p.ctrl = ctrl;
+    p.fid = fid;
+    p.wsum = wsum;
+    p.fmin = fmin;
+    p.tscale = tscale;
+    p.tshift = tshift;
+    p.weights = weights;
+    p.M = M;
+    p.C = C;
+    p.K = K;
+    p.tiles_per_ctrl = (K + 63) / 64;
+    p.ntiles = C * p.tiles_per_ctrl;
+    p.in = in;
+    p.out = out;
+    fill_h0(p.h0, N, h0_diag, h0_offdiag);
+}
+
+static int enqueue_times(hipStream_t s, int N, int in, int out, const double* h0_diag, const double* h0_offdiag, const double* ctrl,
+                         const double* draws, long long draw_cstride, long long C, long long K, int M, const double* tscale,
+                         const double* tshift, const double* weights, double* fid, double* wsum, double* fmin) {
+    rckp::TimesParams p{};
+    fill_times_params(p, N, in, out, h0_diag, h0_offdiag, ctrl, C, K, M, tscale, tshift, weights, fid, wsum, fmin);
+    p.draws = draws;
+    p.draw_cstride = draw_cstride;
+    p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
+    const hipError_t e = (hipError_t)rc_times_launch(N, (void*)s, &p);
+    if (e != hipSuccess) return fail(RC_EHIP, std::string("rc_times_launch: ") + hipGetErrorString(e));
+    return RC_OK;
+}
+
+int rc_mc_fidelity_times_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
+                                   int ring, const double* controllers_dev, const double* draws_dev, long long draws_ctrl_stride,
+                                   long long C, long long K, int M, const double* tscale_dev, const double* tshift_dev,
+                                   const double* weights_dev, double* fid_out_dev, double* wsum_out_dev, double* fmin_out_dev) {
+    bool empty = false;
+    if (int rc = check_times_args(N, in, out, ring, controllers_dev, draws_dev, &draws_ctrl_stride, 0.0, nullptr, C, K, M, weights_dev,
+                                  fid_out_dev, wsum_out_dev, fmin_out_dev, &empty))
+        return rc;
+    if (empty) return RC_OK;
+    RC_HIP_CHECK(hipSetDevice(device));
+    return enqueue_times((hipStream_t)stream, N, in, out, h0_diag, h0_offdiag, controllers_dev, draws_dev, draws_ctrl_stride, C, K, M,
+                         tscale_dev, tshift_dev, weights_dev, fid_out_dev, wsum_out_dev, fmin_out_dev);
+}
+
+int rc_mc_fidelity_times_f64(int device, int N, int in, int out, const double* h0_diag, const double* h0_offdiag, int ring,
+                             const double* controllers, const double* draws, long long draws_ctrl_stride, long long C, long long K,
+                             int M, const double* tscale, const double* tshift, const double* weights, double* fid_out,
+                             double* wsum_out, double* fmin_out) {
+    bool empty = false;
+    if (int rc = check_times_args(N, in, out, ring, controllers, draws, &draws_ctrl_stride, 0.0, nullptr, C, K, M, weights, fid_out,
+                                  wsum_out, fmin_out, &empty))
+        return rc;
+    if (empty) return RC_OK;
+    if (int rc = device_in_range(device)) return rc;
+    std::lock_guard<std::mutex> lk(g_ctx[device].mu);
+    Staging ws;
+    if (int rc = get_ctx(device, &ws.ctx)) return rc;
+    const size_t nb_draw = (draws_ctrl_stride == 0 ? (size_t)K * N * 3 : ((size_t)(C - 1) * draws_ctrl_stride + (size_t)K * N * 3)) *
+                           sizeof(double);
+    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_grid = (size_t)M * sizeof(double);
+    // (an absent grid array stays absent: a slot is declared only for what the caller gave)
+    const int s_ctrl = ws.in(controllers, (size_t)C * (N + 1) * sizeof(double)), s_draw = ws.in(draws, nb_draw),
+              s_scale = tscale ? ws.in(tscale, nb_grid) : -1, s_shift = tshift ? ws.in(tshift, nb_grid) : -1,
+              s_wts = weights ? ws.in(weights, nb_grid) : -1, s_fid = ws.out(fid_out, nb_fid * M), s_wsum = ws.out(wsum_out, nb_fid),
+              s_fmin = ws.out(fmin_out, nb_fid);
+    if (int rc = ws.stage_in()) return rc;
+    if (int rc = enqueue_times(ws.ctx->stream, N, in, out, h0_diag, h0_offdiag, ws.ptr(s_ctrl), ws.ptr(s_draw), draws_ctrl_stride, C, K, M,
+                               s_scale >= 0 ? ws.ptr(s_scale) : nullptr, s_shift >= 0 ? ws.ptr(s_shift) : nullptr,
+                               s_wts >= 0 ? ws.ptr(s_wts) : nullptr, ws.ptr(s_fid), ws.ptr(s_wsum), ws.ptr(s_fmin)))
+        return rc;
+    return ws.stage_out();
+}
+
+int rc_mc_fidelity_times_philox_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,
+                                          const double* h0_offdiag, int ring, const double* controllers_dev, unsigned long long seed,
+                                          unsigned long long offset, double sigma, const double* sigma_rows_dev, long long C,
+                                          long long K, int M, const double* tscale_dev, const double* tshift_dev,
+                                          const double* weights_dev, double* fid_out_dev, double* wsum_out_dev, double* fmin_out_dev) {
+    bool empty = false;
+    if (int rc = check_times_args(N, in, out, ring, controllers_dev, nullptr, nullptr, sigma, sigma_rows_dev, C, K, M, weights_dev,
+                                  fid_out_dev, wsum_out_dev, fmin_out_dev, &empty))
+        return rc;
+    if (empty) return RC_OK;
+    RC_HIP_CHECK(hipSetDevice(device));
+    rckp::TimesParams p{};
+    fill_times_params(p, N, in, out, h0_diag, h0_offdiag, controllers_dev, C, K, M, tscale_dev, tshift_dev, weights_dev, fid_out_dev,
+                      wsum_out_dev, fmin_out_dev);
+    p.seed = seed;
+    p.offset = offset;
+    p.sigma_rows = sigma_rows_dev;
+    p.sigma = sigma;
+    const hipError_t e = (hipError_t)rc_times_philox_launch(N, stream, &p);
+    if (e != hipSuccess) return fail(RC_EHIP, std::string("rc_times_philox_launch: ") + hipGetErrorString(e));
+    return RC_OK;
+}
+
+long long rc_stats_times_general_tiles(int device, int reset) {
+    return read_tile_counter(device, reset, rc_times_counter_addr, "reading the readout-time kernels' tile counter failed");
 }
 
 int rc_mc_fidelity_sens_philox_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,

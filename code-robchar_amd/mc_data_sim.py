@@ -743,6 +743,104 @@ class MCDataSim:
                 direction[j0:j1, :nvalid] = res["direction"].reshape(j1 - j0, nvalid, N, 3)
         return {"noises": noises.tolist(), "fav": fav.tolist(), "dfav_dlogsigma": slope.tolist(), "direction": direction.tolist()}
 
+    # ------------------------------------------------------------------ metrics on a grid of readout times
+    _READOUT_MAX_SLAB_BYTES = 1 << 30    # device bytes of the M fidelity slabs of one launch of `get_readout_dict`
+
+    def get_readout_dict(self, training_noise: str = None, noises: np.ndarray = None, algoname=None, tscale=None, tshift=None,
+                         samples: int = None, seed: int = None) -> dict:
+        """The metrics as a function of the READOUT TIME - reading out early, late, or anywhere in a window - per algorithm, grid
+        time, sigma level and controller:
+
+            {algo: {"noises": [L], "tscale": [M], "tshift": [M], "rim": [M][L][C], "std": [M][L][C], "worst": [M][L][C],
+                    "window_rim": [L][C]}}                                                              (nested lists)
+
+        Grid time j of a controller with time entry T is t_j = |T tscale_j + tshift_j| (`backend.readout_times`; an absent array
+        is all 1 / all 0, M <= 64).  `rim`, `std` and `worst` are the centre values of `backend.reduce_metrics` ("rim1", "std",
+        "min", all positive) over K = `samples` (default: `bootreps`) draws at the level, read out at t_j; `window_rim` is 1 - the
+        mean over the draws of each sample's WORST fidelity on the grid (min_j F_j).  Controllers padded up to `numcontrollers`
+        are NaN.
+
+        The eigen decomposition of a sample is computed once and evaluated at the M times
+        (`noise_model.fidelity_over_times_philox`).  Draws as in `get_sensitivity_dict`: counter-based, generated inside the
+        kernel whatever `rng_mode` says, stream `seed` (default: the instance's), per algorithm ONE launch over the L * C' rows
+        - the controller rows tiled L times, one sigma per row -, split by level only where the M slabs would exceed a private
+        cap on device bytes (or the launch's tile limit).  Level j, controller c, draw k, site i, slot s is stream element
+        ((j C' + c) K + k) 3 N + 3 i + s, offsets from 0 for EVERY algorithm; every grid time sees the SAME draws.  Neither
+        NumPy's global stream nor the instance's Philox offset is consumed.
+
+        Cached as JSON in `get_mcname(...) + "t"` together with `samples`, `seed` and the grid; the file is reused only when all
+        match (and not written with cache_format="none").  One GPU: raises NotImplementedError under an initialised process
+        group or with `devices=...`."""
+        if self.devices is not None:
+            raise NotImplementedError("get_readout_dict runs on one GPU (devices=... is not supported)")
+        try:
+            import torch.distributed as dist
+            grouped = dist.is_available() and dist.is_initialized()
+        except ImportError:
+            grouped = False
+        if grouped:
+            raise NotImplementedError("get_readout_dict runs on one GPU (not under an initialised process group)")
+        if isinstance(algoname, str):
+            algos = [algoname]
+        elif algoname is None:
+            algos = list(self.algos)
+        else:
+            algos = list(algoname)
+        if noises is None:
+            noises = self.noises
+        if training_noise is None:
+            training_noise = self.training_noise
+        noises = np.asarray(noises, dtype=np.float64).reshape(-1)
+        a, b, _ = backend._times_grid(tscale, tshift, None)
+        K = int(self.bootreps if samples is None else samples)
+        seed = int(self.seed if seed is None else seed)
+        key = {"samples": K, "seed": seed, "tscale": a.tolist(), "tshift": b.tolist()}
+        path = self.get_mcname(training_noise, noises) + "t"
+        table = {}
+        if os.path.exists(path):
+            with open(path, "rb") as fh:
+                cached = json.load(fh)
+            if isinstance(cached, dict) and all(cached.get(k) == v for k, v in key.items()):
+                table = cached.get("readout", {})
+        missing = [name for name in algos if name not in table]
+        for name in missing:
+            table[name] = self._readout_of_algo(name, noises, training_noise, K, seed, a, b)
+        if missing and self.cache_format != "none":
+            with open(path, "w") as fh:
+                json.dump({**key, "readout": table}, fh)
+        return {name: table[name] for name in algos}
+
+    def _readout_of_algo(self, algoname: str, noises: np.ndarray, training_noise, K: int, seed: int, tscale: np.ndarray,
+                         tshift: np.ndarray) -> dict:
+        """One algorithm of `get_readout_dict`: NaN-padded (M, L, C) / (L, C) tables as nested lists."""
+        L, C, N, M = int(noises.size), self.numcontrollers, self.Nspin, int(tscale.size)
+        rows_all = self._controller_rows(algoname, training_noise)
+        nvalid = min(len(rows_all), C)
+        ctrl = np.asarray(rows_all[:nvalid], dtype=np.float64).reshape(nvalid, N + 1)
+        rim, std, worst = (np.full((M, L, C), np.nan) for _ in range(3))
+        window = np.full((L, C), np.nan)
+        host = lambda v: v.cpu().numpy() if backend._is_torch(v) else np.asarray(v)
+        centre = lambda slab: {k: host(v)[0] for k, v in backend.reduce_metrics(slab, q_thresholds=(), overlapped=False).items()
+                               if k in ("rim1", "std", "min")}
+        if nvalid and K and L:
+            per_level = nvalid * K * N * 3               # stream elements of one level
+            tiles = nvalid * ((K + 63) // 64)
+            slab_bytes = (M + 1) * nvalid * K * 8        # the M slabs and the per-sample minimum of one level
+            step = max(1, min(L, self._SENS_MAX_TILES // tiles, self._READOUT_MAX_SLAB_BYTES // slab_bytes))
+            for j0 in range(0, L, step):
+                j1 = min(L, j0 + step)
+                res = self.noise_model.fidelity_over_times_philox(np.tile(ctrl, (j1 - j0, 1)), K, seed, tscale=tscale, tshift=tshift,
+                                                                  want=("fid", "min"), sigma=np.repeat(noises[j0:j1], nvalid),
+                                                                  offset=j0 * per_level)
+                for m in range(M):
+                    red = centre(res["fid"][m])
+                    rim[m, j0:j1, :nvalid] = red["rim1"].reshape(j1 - j0, nvalid)
+                    std[m, j0:j1, :nvalid] = red["std"].reshape(j1 - j0, nvalid)
+                    worst[m, j0:j1, :nvalid] = red["min"].reshape(j1 - j0, nvalid)
+                window[j0:j1, :nvalid] = centre(res["min"])["rim1"].reshape(j1 - j0, nvalid)
+        return {"noises": noises.tolist(), "tscale": tscale.tolist(), "tshift": tshift.tolist(), "rim": rim.tolist(),
+                "std": std.tolist(), "worst": worst.tolist(), "window_rim": window.tolist()}
+
     # ------------------------------------------------------------------ bootstrap error bars of the metrics
     def get_bootstrap_dict(self, training_noise: str = None, noises: np.ndarray = None, algoname=None, n_boot: int = 1000,
                            conf: float = 0.95, seed: int = None) -> dict:

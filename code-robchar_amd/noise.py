@@ -78,6 +78,20 @@ def moments_from_sums(mean, moment):
     return {"fav": fav, "grad_fav": grad_fav, "var": var, "grad_var": grad_var, "std": std, "grad_std": grad_std}
 
 
+def readout_jitter_nodes(sigma_t: float, order: int = 8):
+    """Gauss-Hermite nodes and weights of a Gaussian readout-time jitter of standard deviation `sigma_t`, as the `tshift` and
+    `weights` of `backend.mc_fidelity_times`: with x_j, w_j = numpy.polynomial.hermite.hermgauss(order),
+        tshift_j = sqrt(2) sigma_t x_j,    omega_j = w_j / sqrt(pi)        (sum omega = 1).
+    With them the kernel's "wsum" is each sample's fidelity averaged over t = T + N(0, sigma_t^2), obtained deterministically
+    (exact for fidelities that are polynomials of degree < 2 order in the shift)."""
+    if not (float(sigma_t) >= 0.0 and np.isfinite(sigma_t)):
+        raise ValueError("sigma_t must be finite and non-negative")
+    if not (1 <= int(order) <= backend.MAX_TIMES):
+        raise ValueError(f"order must be in 1 .. {backend.MAX_TIMES}")
+    x, w = np.polynomial.hermite.hermgauss(int(order))
+    return np.sqrt(2.0) * float(sigma_t) * x, w / np.sqrt(np.pi)
+
+
 # Row lengths at which a GPU tensor goes through `backend.tail_select` (the HIP selection kernel) instead of the torch sort: every
 # row length (DESIGN.md, "Tail selection kernel", has the timing of both routes per shape).
 def _tail_select_routed(K: int) -> bool:
@@ -321,6 +335,57 @@ class noise_model_base:
             else:
                 mean[:, 1] -= g2 @ imag
         return res
+
+    # -- the fidelity on a grid of readout times (early / late readout, timing jitter) ---------------------------------------
+    def _times_static(self):
+        diag, off, ring, imag = self._static_terms()
+        if ring:
+            raise NotImplementedError("the readout-time kernels are implemented for the chain topology only")
+        return diag, off, imag
+
+    def fidelity_over_times(self, controllers, draws, tscale=None, tshift=None, weights=None, want=("fid",)):
+        """`backend.mc_fidelity_times` for this model: (C, N+1) controllers x (C, K, N, 3) or (1, K, N, 3) draws, a grid of M readout
+        times t_cj = |T_c tscale_j + tshift_j| -> dict of "fid" (M, C, K), "wsum" (C, K), "min" (C, K) (the entries in `want`) from
+        ONE eigen decomposition per sample.  Chain topology only."""
+        diag, off, imag = self._times_static()
+        if imag.any():
+            if backend._is_torch(draws):
+                draws = draws.clone()
+                import torch
+                draws[..., 1:, 2] += torch.as_tensor(imag, device=draws.device)
+            else:
+                draws = np.array(draws, dtype=np.float64)
+                draws[..., 1:, 2] += imag
+        return backend.mc_fidelity_times(controllers, draws, self.Nspin, self.inspin, self.outspin, tscale=tscale, tshift=tshift,
+                                         weights=weights, want=want, h0_diag=diag, h0_offdiag=off, device=self.device)
+
+    def fidelity_over_times_philox(self, controllers, n_draws: int, seed: int, tscale=None, tshift=None, weights=None,
+                                   want=("fid",), sigma=None, offset: int = 0):
+        """`fidelity_over_times` over `n_draws` counter-based draws per controller generated INSIDE the kernel
+        (`backend.mc_fidelity_times_philox`): no draw tensor, the same bits as `fidelity_over_times(controllers,
+        backend.philox_normal((C, K, N, 3), seed, scale=sigma, offset=offset), ...)`; torch tensors out.  `sigma`: None = the
+        model's current level; a float; or one value per controller row.  Chain topology with real static couplings only."""
+        diag, off, imag = self._times_static()
+        if imag.any():
+            raise NotImplementedError("draws generated inside the readout-time kernel: real static couplings only (complex ones: "
+                                      "fidelity_over_times on a draw tensor)")
+        if sigma is None:
+            sigma = float(self.rng.args.get("scale", self.noise))
+        if not backend._is_torch(controllers):
+            controllers = np.asarray(controllers, dtype=np.float64).reshape(-1, self.Nspin + 1)
+        return backend.mc_fidelity_times_philox(controllers, int(n_draws), self.Nspin, self.inspin, self.outspin, seed, offset=offset,
+                                                sigma=sigma, tscale=tscale, tshift=tshift, weights=weights, want=want, h0_diag=diag,
+                                                h0_offdiag=off)
+
+    def fidelity_readout_jitter_philox(self, controllers, n_draws: int, seed: int, sigma_t: float, order: int = 8, sigma=None,
+                                       offset: int = 0):
+        """(C, K) fidelities, each sample's averaged over a Gaussian jitter of the readout time, t = T + N(0, sigma_t^2), by
+        Gauss-Hermite quadrature of `order` nodes (`readout_jitter_nodes`): the "wsum" of ONE `fidelity_over_times_philox` launch.
+        NumPy array out.  The structured noise is sampled (`n_draws` counter-based draws per row), the timing jitter integrated."""
+        tshift, weights = readout_jitter_nodes(sigma_t, order)
+        res = self.fidelity_over_times_philox(controllers, n_draws, seed, tshift=tshift, weights=weights, want=("wsum",),
+                                              sigma=sigma, offset=offset)["wsum"]
+        return res.cpu().numpy() if backend._is_torch(res) else np.asarray(res)
 
     def noise_sensitivity(self, controllers, draws):
         """What the samples of ONE sigma level say about the neighbourhood of that level, from one kernel launch:

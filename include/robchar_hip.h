@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 15     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 16     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -67,7 +67,9 @@ extern "C" {
                                   13: + rc_lbfgs_state_len, rc_lbfgs_init_f64_async, rc_lbfgs_advance_f64_async,
                                       rc_lbfgs_result_f64_async (additive);
                                   14: + rc_lbfgs_init_box_f64_async, rc_lbfgs_advance_box_f64_async (additive);
-                                  15: + rc_bootstrap_metrics_f64_async, rc_bootstrap_metrics_f64 (additive) */
+                                  15: + rc_bootstrap_metrics_f64_async, rc_bootstrap_metrics_f64 (additive);
+                                  16: + rc_mc_fidelity_times_f64_async, rc_mc_fidelity_times_f64,
+                                      rc_mc_fidelity_times_philox_f64_async, rc_stats_times_general_tiles, RC_MAX_TIMES (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -450,6 +452,52 @@ int rc_bootstrap_metrics_f64(int device, const double* fid, long long C, long lo
  * {in, out} = {0, N-1}), else 0; 0 everywhere when ROBCHAR_PHILOX_FUSED=0 is in the environment (read per call).  The ONE
  * copy of that rule: the sharded entries below and the Python layer (backend.philox_fused_pays) both ask it. */
 int rc_philox_fused_pays(int N, int in, int out);
+
+/* (ABI 16) Fidelity on a grid of readout times from ONE eigen decomposition per sample.  Chain topology, N = 2 .. RC_MAX_NSPIN_FAST,
+ * any (in, out).  The grid has M times, 1 <= M <= RC_MAX_TIMES; for controller row c (time entry T_c, signed as stored)
+ *     t_cj = | T_c tscale[j] + tshift[j] |        product rounded first, sum second (no fused multiply-add), absolute value last:
+ *                                                  NumPy's np.abs(T[:, None] * tscale + tshift), bit for bit
+ *     F_j(c, k) = |<out| exp(-i H_ck t_cj) |in>|^2,   H_ck as in rc_mc_fidelity_f64.
+ * tscale, tshift: [M] each, NULL = all 1 / all 0.  Outputs, each optional (NULL = not wanted; all three NULL: RC_EINVAL "no output"):
+ *     fid_out  [M][C][K]   M slabs, each an ordinary [C][K] fidelity tensor (what rc_reduce_f64, rc_bootstrap_metrics_f64,
+ *                          rc_tail_select_f64_async take); slab j is bit for bit what kernel = RC_KERNEL_TRIDIAG_QL gives for
+ *                          controllers whose time entry is t_cj
+ *     wsum_out [C][K]      acc = weights[0] F_0;  acc = fma(weights[j], F_j, acc), j = 1 .. M - 1: fixed order.  Needs weights [M]
+ *                          (NULL with wsum_out set: RC_EINVAL)
+ *     fmin_out [C][K]      min_j F_j, taken in the order of j
+ * A controller row holding a NaN gives NaN in every output and its draws are not read.  One all-fp64 implicit QL with the
+ * eigenvector rows `in` and `out` per sample (no condition on eigenvalue gaps or cut bonds), then N - 1 table-driven sines and
+ * cosines per time.  Their argument must stay inside the table routine's domain:  |t_cj (lambda_k - lambda_0)| < 2.1e8  for every
+ * eigenvalue lambda_k of H_ck (as for every register-resident chain kernel at the row's own T); beyond it the result is undefined.
+ * A sample whose QL runs into its sweep cap (observed for H = 0 exactly, nothing else) takes a textbook per-sample routine,
+ * counted per tile in rc_stats_times_general_tiles.
+ * Argument checks before any HIP call: N, in, out, C, K as in rc_mc_fidelity_f64 (RC_EINVAL); N > RC_MAX_NSPIN_FAST or ring != 0:
+ * RC_ENOSUP; M outside 1 .. RC_MAX_TIMES, no output, wsum_out without weights, draws_ctrl_stride overlapping controllers:
+ * RC_EINVAL; C or K = 0: RC_OK, nothing written; controllers or draws NULL: RC_EINVAL.
+ * draws_ctrl_stride: K*N*3 (or negative) for one draw block per controller, 0 for ONE set of K draws shared by every controller.
+ * _async: enqueue-only - device pointers for controllers, draws, tscale, tshift, weights and the outputs; one kernel launch on
+ * `stream`, no allocation, no synchronisation, capturable into a graph.  The blocking entry takes host or device arrays. */
+#define RC_MAX_TIMES 64
+int rc_mc_fidelity_times_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
+                                   int ring, const double* controllers_dev, const double* draws_dev, long long draws_ctrl_stride,
+                                   long long C, long long K, int M, const double* tscale_dev, const double* tshift_dev,
+                                   const double* weights_dev, double* fid_out_dev, double* wsum_out_dev, double* fmin_out_dev);
+int rc_mc_fidelity_times_f64(int device, int N, int in, int out, const double* h0_diag, const double* h0_offdiag, int ring,
+                             const double* controllers, const double* draws, long long draws_ctrl_stride, long long C, long long K,
+                             int M, const double* tscale, const double* tshift, const double* weights, double* fid_out,
+                             double* wsum_out, double* fmin_out);
+/* The same with the counter-based draws generated inside the kernel: sample (c, k), site i, slot s is element
+ *     offset + ((c K + k) N + i) 3 + s      of stream `seed` (rc_draws_philox_f64_async), scaled by sigma_rows_dev[c], or by `sigma`
+ * when sigma_rows_dev is NULL (then a negative or non-finite sigma is RC_EINVAL).  Every output is bit-identical to
+ * rc_draws_philox_f64_async into a [C][K][N][3] tensor followed by rc_mc_fidelity_times_f64_async.  Enqueue-only. */
+int rc_mc_fidelity_times_philox_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,
+                                          const double* h0_offdiag, int ring, const double* controllers_dev, unsigned long long seed,
+                                          unsigned long long offset, double sigma, const double* sigma_rows_dev, long long C,
+                                          long long K, int M, const double* tscale_dev, const double* tshift_dev,
+                                          const double* weights_dev, double* fid_out_dev, double* wsum_out_dev, double* fmin_out_dev);
+/* Diagnostic (ABI 16): the counter of rc_stats_grad_general_tiles for the two readout-time kernels. */
+long long rc_stats_times_general_tiles(int device, int reset);
+
 
 /* Non-Hermitian variant: `diag_imag_dev` [C][K][N] (or NULL) is added to the diagonal as an IMAGINARY part,
  * H[i][i] += 1j * diag_imag.  Chains up to N = 12: a lane-per-sample complex symmetric QL kernel (the couplings stay
