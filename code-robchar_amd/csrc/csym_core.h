@@ -203,8 +203,7 @@ RC_HD bool csym_fidelity(const double* x, const double* h0d, const double* h0o, 
         n1r += fma(s.zr[1][k], s.zr[1][k], -s.zi[1][k] * s.zi[1][k]);
         n1i = fma(s.zr[1][k], s.zi[1][k], n1i);
         double sk, ck;
-        if (kTableSinCos) sincos_table(Tk * s.dr[k], sctab, sk, ck);
-        else sincos_reduced(T * s.dr[k], sk, ck);
+        sincos_table(Tk * s.dr[k], sctab, sk, ck);
         const double amp = exp_small(T * s.di[k]);
         const double cr = amp * ck, ci = -amp * sk;
         re = fma(wr, cr, fma(-wi, ci, re));

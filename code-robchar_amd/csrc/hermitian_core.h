@@ -19,11 +19,9 @@
 namespace rc {
 
 // Up to this size the lane-per-sample ring routes hold the dense lower triangle in registers (Householder reduction); above,
-// the folded band reduction further down (ring_fold_*, round 5).
-#ifndef RC_RING_DENSE_MAX_N
-#define RC_RING_DENSE_MAX_N 10
-#endif
-constexpr int kRingDenseMaxN = RC_RING_DENSE_MAX_N;
+// the folded band reduction further down (ring_fold_*, round 5).  (The fold for every size: 1-2.5 % faster at N = 5, 7, equal
+// at 10, same fuzz worst cases - profiles/r05_ab_ring_fold.txt, r05_fuzz_ring_foldall.txt; the dense route is the fuzzed one.)
+constexpr int kRingDenseMaxN = 10;
 template <int N>
 RC_HD void ring_fold_tridiag_rows(const double (&d)[N], const double (&hr)[N], const double (&hi)[N], double corner, int in, int out,
                                   TriEig<N, 4>& s);
@@ -184,8 +182,7 @@ RC_HD double complex_rows_fidelity(const TriEig<N, 4>& s, double T, const double
         const double wr = fma(s.z[2][k], s.z[0][k], s.z[3][k] * s.z[1][k]);
         const double wi = fma(s.z[3][k], s.z[0][k], -s.z[2][k] * s.z[1][k]);
         double sk, ck;
-        if (kTableSinCos) sincos_table(Tk * (s.d[k] - s.d[0]), sctab, sk, ck);
-        else sincos_reduced(T * (s.d[k] - s.d[0]), sk, ck);
+        sincos_table(Tk * (s.d[k] - s.d[0]), sctab, sk, ck);
         // (wr + i wi)(c - i s)
         re = fma(wr, ck, fma(wi, sk, re));
         im = fma(wi, ck, fma(-wr, sk, im));
@@ -832,8 +829,7 @@ RC_HD bool ring_fidelity_mixed(const double* x, const double* h0d, const double*
         } else {
             const double dl = lam[k] - lam[0];
             double sk, ck;
-            if (kTableSinCos) sincos_table(Tk * dl, sctab, sk, ck);
-            else sincos_reduced(T * dl, sk, ck);
+            sincos_table(Tk * dl, sctab, sk, ck);
             re = fma(wr, ck, fma(wi, sk, re));                    // (wr + i wi)(c - i s)
             im = fma(wi, ck, fma(-wr, sk, im));
             if (kSumRuleGuard && kSumRuleMoments >= 3) {

@@ -134,11 +134,9 @@ template <int N, int MODE>
 __global__ __launch_bounds__(64, dir_bond_min_waves(N)) void mc_fid_dir_bond_kernel(const DirParams p) {
     __shared__ __attribute__((aligned(16))) double sctab[128];
     const int lane = threadIdx.x;
-    if (rc::kTableSinCos) {
-        const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-        reinterpret_cast<double2*>(sctab)[lane] = ent;
-        __syncthreads();
-    }
+    const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
+    reinterpret_cast<double2*>(sctab)[lane] = ent;
+    __syncthreads();
     const long long nb = (long long)p.counts[0];
     const long long i = (long long)blockIdx.x * 64 + lane;
     if ((long long)blockIdx.x * 64 >= nb) return;               // wave-uniform: the grid is sized for the worst case
@@ -186,11 +184,9 @@ template <int N>
 __global__ __launch_bounds__(64, csym_min_waves(N)) void mc_fid_dir_diag_kernel(const DirParams p) {
     __shared__ __attribute__((aligned(16))) double sctab[128];
     const int lane = threadIdx.x;
-    if (rc::kTableSinCos) {
-        const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-        reinterpret_cast<double2*>(sctab)[lane] = ent;
-        __syncthreads();
-    }
+    const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
+    reinterpret_cast<double2*>(sctab)[lane] = ent;
+    __syncthreads();
     const long long nd = p.n - (long long)p.counts[0];
     const long long i = (long long)blockIdx.x * 64 + lane;
     if ((long long)blockIdx.x * 64 >= nd) return;

@@ -12,28 +12,22 @@
 // adjugate (its end-to-end specialisation when {in,out} = {0,N-1}); the rows mode stays selectable as a cross-check.
 // Round 2: the eigenvalue-only modes at N = 3..13 compute their eigenvalues in mixed precision (tridiag_core.h:
 // fp32 QL rotations + one fp64 Halley step): N = 7 end-to-end 52-56 us, general adjugate 55-59 us.
-#ifndef RC_WAVES_SMALL
-#define RC_WAVES_SMALL 5
-#endif
+constexpr int kWavesSmall = 5;
 // Chosen from the ISA's VGPR need per instantiation (`make asm`; tests/test_asm_resources.py fails on any spill): a
 // wave limit of W allows floor(512 / W) VGPRs (multiples of 8).  Residency above ~4 waves buys nothing,
-// a spilled register costs scratch traffic in the innermost loop.  -DRC_WAVES_N=<n> -DRC_WAVES_W=<w> overrides one N
-// (all modes) for A/B timing.
+// a spilled register costs scratch traffic in the innermost loop (A/B of the table: profiles/r02_residency_variants.txt).
 constexpr int fid_min_waves(int n, int mode) {
-#if defined(RC_WAVES_N) && defined(RC_WAVES_W)
-    if (n == RC_WAVES_N) return RC_WAVES_W;
-#endif
     // (general adjugate at N = 13: 268 registers with the mixed-precision state - one wave; N >= 14 runs the all-fp64 QL.
     // With all THREE moment rules of the a-posteriori guard (-DRC_SUM_RULE_MOMENTS=3) four picked matrix entries stay alive
     // through the eigenvalue phase: N = 8 then needs 3 waves instead of 4, N = 14..16 one instead of 2)
     // (N = 17 .. 24, round 5: one wave - 14 N doubles of state and the unrolled recurrences of the weights)
     if (mode == rc::kWeightsAdjugate)
         return n >= 17 ? 1
-               : rc::kSumRuleMoments >= 3 ? (n <= 6 ? RC_WAVES_SMALL : (n <= 7 ? 4 : (n <= 8 ? 3 : (n >= 13 ? 1 : 2))))
-                                          : (n <= 6 ? RC_WAVES_SMALL : (n <= 8 ? 4 : (n == 13 ? 1 : 2)));
-    if (mode == rc::kWeightsRows) return n <= 8 ? RC_WAVES_SMALL : (n <= 12 ? 3 : 2);
+               : rc::kSumRuleMoments >= 3 ? (n <= 6 ? kWavesSmall : (n <= 7 ? 4 : (n <= 8 ? 3 : (n >= 13 ? 1 : 2))))
+                                          : (n <= 6 ? kWavesSmall : (n <= 8 ? 4 : (n == 13 ? 1 : 2)));
+    if (mode == rc::kWeightsRows) return n <= 8 ? kWavesSmall : (n <= 12 ? 3 : 2);
     // kWeightsEnds
-    return n <= 6 ? RC_WAVES_SMALL : (n <= 8 ? 4 : (n <= 10 ? 3 : (n <= 14 ? 2 : 1)));
+    return n <= 6 ? kWavesSmall : (n <= 8 ? 4 : (n <= 10 ? 3 : (n <= 14 ? 2 : 1)));
 }
 // staging phases: the LDS buffer (64/phases * 3N doubles per wave) must not cap residency below the register limit
 constexpr int fid_phases(int n, int mode) { return n <= 2 ? 1 : (n <= 8 ? 2 : 4); }
@@ -71,10 +65,9 @@ __global__ __launch_bounds__(64, fid_min_waves(N, MODE)) void mc_fid_chain_kerne
 
     const int lane = threadIdx.x;
     const long long tile = blockIdx.x;             // wave-uniform
-    if (rc::kTableSinCos) {                        // lane k copies entry k; consumed long after the staging waits
-        const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-        reinterpret_cast<double2*>(sctab)[lane] = ent;
-    }
+    // lane k copies entry k; consumed long after the staging waits
+    const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
+    reinterpret_cast<double2*>(sctab)[lane] = ent;
     // The staging phase is a handful of instructions separated by memory latency; issued at raised priority it
     // is not starved by the older waves of the SIMD that are in their (VALU-dense) compute phase, so its
     // latency overlaps their arithmetic instead of stretching (measured: staging 31k -> 4k ticks per tile).
@@ -160,7 +153,7 @@ __global__ __launch_bounds__(64, fid_min_waves(N, MODE)) void mc_fid_chain_kerne
         }
     }
     __builtin_amdgcn_s_setprio(0);
-    if (rc::kTableSinCos) __syncthreads();         // the table copy has landed (one wave per workgroup: no wait)
+    __syncthreads();                               // the table copy has landed (one wave per workgroup: no wait)
 #ifdef RC_STAMPS
     const long long t_loaded = __builtin_amdgcn_s_memtime();
 #endif
@@ -181,7 +174,7 @@ __global__ __launch_bounds__(64, fid_min_waves(N, MODE)) void mc_fid_chain_kerne
     // (N >= 17: no rows-mode QL in registers - a bad lane goes straight to the LDS routine below)
     constexpr bool kRepairInRegisters = MODE != rc::kWeightsRows && N <= RC_MAX_NSPIN_FAST;
     unsigned long long badmask = __ballot(lane < nk && !ok);
-    if (RC_UNLIKELY(badmask != 0ull)) {
+    if (badmask != 0ull) {
         if (lane == 0) atomicAdd(&g_general_tiles, 1ull);
         // Rare: some samples of this tile left the fast path (degenerate eigenvalue pair - the eigenvalue-only weights need
         // distinct eigenvalues -, sweep cap, overflow).  REPAIR, step 1: those lanes alone run the register-resident QL
@@ -202,7 +195,7 @@ __global__ __launch_bounds__(64, fid_min_waves(N, MODE)) void mc_fid_chain_kerne
             badmask = __ballot(bad && !ok2);
         }
     }
-    if (RC_UNLIKELY(badmask != 0ull)) {
+    if (badmask != 0ull) {
         // Step 2 (last resort: the rows-mode QL hit its sweep cap too - not observed): the textbook per-sample routine,
         // CH lanes at a time, work vectors (4N doubles per sample) in the LDS staging buffer, which is free now.
         constexpr int CH = (SP * G) / (4 * N);
@@ -376,11 +369,9 @@ __global__ __launch_bounds__(64, ring_min_waves(N)) void mc_fid_ring_kernel(cons
     constexpr int SP = 64 / fid_phases(N, rc::kWeightsRows);
     __shared__ __attribute__((aligned(16))) double stage[SP * G];
     __shared__ __attribute__((aligned(16))) double sctab[128];
-    if (rc::kTableSinCos) {
-        const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[threadIdx.x];
-        reinterpret_cast<double2*>(sctab)[threadIdx.x] = ent;
-        __syncthreads();                           // (one wave per workgroup: no wait)
-    }
+    const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[threadIdx.x];
+    reinterpret_cast<double2*>(sctab)[threadIdx.x] = ent;
+    __syncthreads();                           // (one wave per workgroup: no wait)
     ring_tile_fp64<N>(p, corner, blockIdx.x, stage, sctab);
 }
 
@@ -395,9 +386,6 @@ __global__ __launch_bounds__(64, ring_min_waves(N)) void mc_fid_ring_kernel(cons
 // (the guard's accumulators cost N = 5 and N = 7 one wave of residency: 5 -> 4, 4 -> 3 - measured together with the m = 0
 // rule at +1.7 % for both sizes; with all three moment rules, -DRC_SUM_RULE_MOMENTS=3, N = 9 goes 3 -> 2 as well)
 constexpr int ring_mixed_min_waves(int n) {
-#if defined(RC_RWAVES_N) && defined(RC_RWAVES_W)
-    if (n == RC_RWAVES_N) return RC_RWAVES_W;      // residency experiments (scripts/build_variant.sh)
-#endif
     return n <= 4 ? 5 : (n <= 6 ? 4 : (n <= 8 ? 3 : (n == 9 ? (rc::kSumRuleMoments >= 3 ? 2 : 3) : (n <= 13 ? 2 : 1))));
 }
 
@@ -419,10 +407,8 @@ __global__ __launch_bounds__(64, ring_mixed_min_waves(N)) void mc_fid_ring_mixed
     // the list counters alternate between calls: this call appends to `count` and empties the one the next call will use
     // (whoever read that one - the previous call's repair kernel - finished before this kernel started: stream order)
     if (blockIdx.x == 0 && lane == 0) *rl.clear = 0ull;
-    if (rc::kTableSinCos) {
-        const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-        reinterpret_cast<double2*>(sctab)[lane] = ent;
-    }
+    const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
+    reinterpret_cast<double2*>(sctab)[lane] = ent;
     __builtin_amdgcn_s_setprio(3);
     const long long c = tile / p.tiles_per_ctrl;
     const long long kb = (tile - c * p.tiles_per_ctrl) * 64;
@@ -444,7 +430,7 @@ __global__ __launch_bounds__(64, ring_mixed_min_waves(N)) void mc_fid_ring_mixed
     double gl[G];
     stage_tile_draws<G, PH>(src, nk, lane, p.align16, stage, gl);
     __builtin_amdgcn_s_setprio(0);
-    if (rc::kTableSinCos) __syncthreads();
+    __syncthreads();
     double f = 0.0;
     bool ok = true;
     int extra = 0;
@@ -476,11 +462,9 @@ __global__ __launch_bounds__(64, 1) void mc_fid_ring_repair_kernel(const FidPara
     __shared__ __attribute__((aligned(16))) double work[6 * N * 64];
     __shared__ __attribute__((aligned(16))) double sctab[128];
     const int lane = threadIdx.x;
-    if (rc::kTableSinCos) {
-        const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-        reinterpret_cast<double2*>(sctab)[lane] = ent;
-        __syncthreads();
-    }
+    const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
+    reinterpret_cast<double2*>(sctab)[lane] = ent;
+    __syncthreads();
     const long long count = (long long)*rl.count;
 #pragma unroll 1
     for (long long i0 = (long long)blockIdx.x * 64; i0 < count; i0 += (long long)gridDim.x * 64) {

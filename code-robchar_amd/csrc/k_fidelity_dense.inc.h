@@ -489,11 +489,9 @@ template <int N>
 __global__ __launch_bounds__(64, csym_min_waves(N)) void mc_fid_csym_kernel(const ExpmParams p) {
     __shared__ __attribute__((aligned(16))) double sctab[128];
     const int lane = threadIdx.x;
-    if (rc::kTableSinCos) {
-        const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-        reinterpret_cast<double2*>(sctab)[lane] = ent;
-        __syncthreads();
-    }
+    const double2 ent = reinterpret_cast<const double2*>(g_sincos_table)[lane];
+    reinterpret_cast<double2*>(sctab)[lane] = ent;
+    __syncthreads();
     const long long sidx = (long long)blockIdx.x * 64 + lane;
     if (sidx >= p.C * p.K) return;
     const long long c = sidx / p.K, k = sidx - c * p.K;

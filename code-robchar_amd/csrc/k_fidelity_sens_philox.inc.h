@@ -29,12 +29,9 @@
 //
 // Included by robchar_grad.hip inside its anonymous namespace after k_fidelity_sens.inc.h; not a stand-alone header.
 
-// (-DRC_SENS_PHILOX_REG_MAX=<n>, scripts/build_variant.sh: single-pass sizes above n hold their draws in LDS too - N = 7 then fits
-// two waves per SIMD, 256 registers - for A/B timing against the registers)
-#ifndef RC_SENS_PHILOX_REG_MAX
-#define RC_SENS_PHILOX_REG_MAX 9
-#endif
-constexpr bool sens_philox_hold_in_registers(int n) { return rc::sens_passes(n) == 1 && n <= RC_SENS_PHILOX_REG_MAX; }
+// (single-pass sizes above 9 hold their draws in LDS too; with 6 here, N = 7 fits two waves per SIMD, 256 registers - the A/B
+// against the registers: DESIGN.md, the sensitivity kernels)
+constexpr bool sens_philox_hold_in_registers(int n) { return rc::sens_passes(n) == 1 && n <= 9; }
 // from the listing: 60 / 108 registers at N = 2, 3 (four waves), 152 / 196 / 252 at N = 4 .. 6 (two), from N = 7
 // (294: the 42 held values beside mc_fid_sens_kernel's 256) one wave
 constexpr int sens_philox_min_waves(int n) { return n <= 3 ? 4 : ((n <= 6 || (n == 7 && !sens_philox_hold_in_registers(7))) ? 2 : 1); }

@@ -130,7 +130,7 @@ __global__ __launch_bounds__(64, times_min_waves(N)) void mc_fid_times_kernel(co
         if (lane < nk && ok) rc::times_loop_fast<N>(dl, w, x[N], p.M, p.tscale, p.tshift, p.weights, sctab, dst, acc);
     }
     const unsigned long long badmask = __ballot(lane < nk && !ok);
-    if (RC_UNLIKELY(badmask != 0ull)) {
+    if (badmask != 0ull) {
         // Rare (H = 0 exactly; times_core.h): some lane's QL ran into the sweep cap.  Those lanes take the textbook routine, CH at
         // a time, work vectors (4 N doubles per sample) in the staging buffer, which is free now; draws re-read from HBM; the time
         // loop inside.
@@ -218,7 +218,7 @@ __global__ __launch_bounds__(64, times_philox_min_waves(N)) void mc_fid_times_ph
         if (lane < nk && ok) rc::times_loop_fast<N>(dl, w, x[N], p.M, p.tscale, p.tshift, p.weights, sctab, dst, acc);
     }
     const unsigned long long badmask = __ballot(lane < nk && !ok);
-    if (RC_UNLIKELY(badmask != 0ull)) {
+    if (badmask != 0ull) {
         // rare: the textbook routine, CH lanes at a time; their draws are regenerated element by element into LDS
         if (lane == 0) atomicAdd(&g_times_general_tiles, 1ull);
         const bool bad = (badmask >> lane) & 1ull;

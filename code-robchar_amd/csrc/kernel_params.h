@@ -14,12 +14,8 @@ struct StaticH {          // passed by value in the kernarg segment: no device a
 // Cache policy of the draw stream: the `aux` operand of the LDS-DMA loads (__builtin_amdgcn_global_load_lds) of
 // mc_fid_chain_kernel and stage_tile_draws.  The draws are read exactly once per launch and are larger than L2 (168 MB at
 // 100 x 10 000, N = 7), so they stream: 2 = the `nt` bit (global_load_lds_dword[x4] ... nt), 0 = the default policy.
-// Changes no arithmetic (profiles/launch_boundary_ab.txt).  -DRC_DRAW_LOAD_AUX=0 builds the other side for A/B timing
-// (scripts/build_variant.sh).
-#ifndef RC_DRAW_LOAD_AUX
-#define RC_DRAW_LOAD_AUX 2
-#endif
-constexpr int kDrawLoadAux = RC_DRAW_LOAD_AUX;
+// Changes no arithmetic (profiles/launch_boundary_ab.txt: the A/B against the default policy).
+constexpr int kDrawLoadAux = 2;
 
 struct FidParams {
     const double* ctrl;    // [C][N+1]

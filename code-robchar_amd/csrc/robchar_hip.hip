@@ -1510,24 +1510,12 @@ long long rc_debug_nt_store_tiles(long long tiles) { return g_nt_store_tiles.exc
 
 int rc_version(void) { return RC_ABI_VERSION; }
 
-// Which compile-time switches of this build change RESULTS or disable a safety net (0 = the product build).  The timing
-// experiments of scripts/build_variant.sh knowingly return wrong fidelities for some samples; a library built with one of them
-// must never be taken for the product (code-robchar_amd/_lib.py refuses it unless ROBCHAR_ALLOW_EXPERIMENT_LIB=1; bench.py
-// records the value).
+// Which compile-time switches of this build change RESULTS or disable a safety net (0 = the product build).  A library built
+// with one of them must never be taken for the product (code-robchar_amd/_lib.py refuses the ones in RC_BUILD_WRONG_RESULTS_MASK
+// - timing experiments of earlier trees, which knowingly returned wrong fidelities - unless ROBCHAR_ALLOW_EXPERIMENT_LIB=1;
+// bench.py records the value).
 int rc_build_flags(void) {
     int f = 0;
-#ifdef RC_EXPERIMENT_NO_STEPPING
-    f |= RC_BUILD_EXPERIMENT_NO_STEPPING;
-#endif
-#ifdef RC_EXPERIMENT_STEP_NOT_RUN
-    f |= RC_BUILD_EXPERIMENT_STEP_NOT_RUN;
-#endif
-#ifdef RC_EXPERIMENT_FALLBACK_NOT_RUN
-    f |= RC_BUILD_EXPERIMENT_FALLBACK_NOT_RUN;
-#endif
-#ifdef RC_EXPERIMENT_PHILOX_NOSTORE
-    f |= RC_BUILD_EXPERIMENT_PHILOX_NOSTORE;
-#endif
 #ifdef RC_DEV_FEW_N
     f |= RC_BUILD_DEV_FEW_N;
 #endif

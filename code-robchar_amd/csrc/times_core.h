@@ -102,8 +102,7 @@ RC_HD double times_phase_fid(const double (&dl)[N], const double (&w)[N], double
 #pragma unroll
     for (int k = 1; k < N; ++k) {
         double sk, ck;
-        if (kTableSinCos) sincos_table(Tk * dl[k], sctab, sk, ck);
-        else sincos_reduced(t * dl[k], sk, ck);
+        sincos_table(Tk * dl[k], sctab, sk, ck);
         re = fma(w[k], ck, re);
         im = fma(-w[k], sk, im);
     }

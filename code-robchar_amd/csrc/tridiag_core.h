@@ -38,22 +38,19 @@
 #define RC_HD inline
 #endif
 
-// Branch-weight hints for the rare paths (stepping path, tile-wide fp64 QL, repair): with -DRC_EXPECT_HINTS=1 the block
-// placement moves the cold code behind the kernel's hot path instead of between its stages (the hot path then falls through
-// where it otherwise takes three branches over ~5 KB of cold instructions).  Measured (round 4, same-box A/B, two rounds of
-// 300 launches, profiles/r04_ab_expect_hints.txt): N = 7 -0.7 %, N = 10 XXZ +1.4 %, shipped controllers -0.5 %, ring +0.5 % -
-// noise; the ~50 VALU instructions per wave by which a build WITHOUT the stepping path is shorter (PMC: 1 327 against 1 377)
-// are the acceptance test itself (the step / critical-point maxima and the bound), not the code's presence.  Off.
-#ifndef RC_EXPECT_HINTS
-#define RC_EXPECT_HINTS 0
+// Switches of rejected experiments and of settled A/Bs that earlier trees had: a command line that still
+// names one must not quietly build the product.
+#if defined(RC_EXPECT_HINTS) || defined(RC_BATCH_INVERSE) || defined(RC_TABLE_SINCOS) || defined(RC_SHIFT_NODIV) || \
+    defined(RC_CLOSED_2X2) || defined(RC_ABERTH_FIRST) || defined(RC_POLISH_LARGE_N) || defined(RC_ALWAYS_DISTINCT_CHECK) || \
+    defined(RC_SUM_RULE_ENDS) || defined(RC_STEP2_NEWTON_ALL) || defined(RC_STEP_ALL_FIRST) || \
+    defined(RC_EXPERIMENT_NO_STEPPING) || defined(RC_EXPERIMENT_STEP_NOT_RUN) || defined(RC_EXPERIMENT_FALLBACK_NOT_RUN) || \
+    defined(RC_EXPERIMENT_PHILOX_NOSTORE) || defined(RC_FAST_EPS) || defined(RC_F32_EPS) || defined(RC_HALLEY_ACCEPT) || \
+    defined(RC_HALLEY_CRITICAL) || defined(RC_SUM_RULE_TOL) || defined(RC_MIXED_MAX_N) || defined(RC_ENDS_AMPLITUDE_MAX_N) || \
+    defined(RC_WAVES_SMALL) || defined(RC_WAVES_N) || defined(RC_WAVES_W) || defined(RC_RWAVES_N) || defined(RC_RWAVES_W) || \
+    defined(RC_DRAW_LOAD_AUX) || defined(RC_RING_DENSE_MAX_N) || defined(RC_SENS_PHILOX_REG_MAX)
+#error "this build names an RC_* switch that was removed: the experiment it selected is recorded in DESIGN.md section 8, the constants are plain constexpr now"
 #endif
-#if RC_EXPECT_HINTS
-#define RC_LIKELY(x) __builtin_expect(!!(x), 1)
-#define RC_UNLIKELY(x) __builtin_expect(!!(x), 0)
-#else
-#define RC_LIKELY(x) (x)
-#define RC_UNLIKELY(x) (x)
-#endif
+// (Branch-weight hints on the rare paths - __builtin_expect - measured as noise: profiles/r04_ab_expect_hints.txt.)
 
 #if defined(RC_FLAG_STATS) && !defined(__HIP_DEVICE_COMPILE__)
 void rc_flag_stats_hook(int n, unsigned roots, double maxd, const double* lam);
@@ -74,26 +71,8 @@ constexpr double kEps = 2.220446049250313e-16;   // DBL_EPSILON: split tolerance
 // tol = 1e-10, 2e-12 at 1e-9, 2e-10 at 1e-8 - quadratic as expected) and saves the last, already-converged sweep of
 // most eigenvalues: 12 % fewer rotations per 64-sample tile.  Eigenvector rows are first order in e_l, so the rows
 // mode keeps DBL_EPSILON.
-#ifndef RC_FAST_EPS
-#define RC_FAST_EPS 1e-10
-#endif
-constexpr double kFastEpsValues = RC_FAST_EPS;
+constexpr double kFastEpsValues = 1e-10;
 constexpr int kMaxSweepsPerEig = 40;             // hard cap on QL iterations per eigenvalue (general path)
-#ifndef RC_BATCH_INVERSE
-#define RC_BATCH_INVERSE 1
-#endif
-constexpr bool kBatchInverse = RC_BATCH_INVERSE;   // adjugate weights: one reciprocal per batch of weights (ends_weights)
-#ifndef RC_TABLE_SINCOS
-#define RC_TABLE_SINCOS 1
-#endif
-constexpr bool kTableSinCos = RC_TABLE_SINCOS;     // fast path: table-driven sin/cos (sincos_table)
-#ifndef RC_SHIFT_NODIV
-#define RC_SHIFT_NODIV 1
-#endif
-#ifndef RC_CLOSED_2X2
-#define RC_CLOSED_2X2 1
-#endif
-constexpr bool kClosedForm2x2 = RC_CLOSED_2X2;   // fast path: solve the last 2x2 block directly instead of sweeping
 // Mixed path, after the all-fp64 QL: pairs closer than this * scale need eigenvectors (repair path).  END-TO-END weights
 // (numerator = the constant prod e): the two weights of a pair are +-A / gap with the SAME computed gap and a smooth A, their
 // joint contribution is a divided difference of a smooth function - accurate down to gaps at the eigenvalues' own rounding
@@ -111,15 +90,6 @@ constexpr double kDegenerateGapAdjugate = 4e-6;
 #ifndef RC_KEEP_SETTLED
 #define RC_KEEP_SETTLED 1
 #endif
-// One Halley step on the all-fp64 QL's eigenvalues at N >= 14 (general adjugate mode; see chain_fidelity_fast).  Measured
-// (round 4, profiles/r04_ab_polish_large_n.txt): the fuzz block's N = 16 worst case 1.03e-11 -> 6.4e-12 (lock-step host
-// emulation of that configuration: 9.2e-12 -> 4.1e-13), kernel +16 % at N = 14 and N = 16 - while the campaign's overall worst
-// (1.1e-11: adjugate numerators beside a pair 2e-5 of the scale apart at |T| = 63, N = 12, and the ring) is set elsewhere.  Off:
-// 16 % of two non-benchmark sizes for no change of the bound the kernels can claim.
-#ifndef RC_POLISH_LARGE_N
-#define RC_POLISH_LARGE_N 0
-#endif
-constexpr bool kPolishLargeN = RC_POLISH_LARGE_N;
 constexpr int kFastSweepCap = 10;                // fast path: more sweeps than this for one eigenvalue -> general path
 
 // ---- hardware seeds ---------------------------------------------------------------------------------------
@@ -188,21 +158,13 @@ constexpr bool kMixedEig = RC_MIXED_EIG;
 // -6 / -12 / -13 / -16 / -25 / -27 % kernel time; N = 9 / 10 / 11 / 12 / 13: -19 / -14 (XXZ: -18) / -11 / -8 / -2 (XXZ: -8) %
 // (adjugate mode: -20 / -22 / -14 / -10 / -5 %).  Above, the fp64 (d, e^2) kept through the fp32 phase cost more registers
 // than the kernels have without spilling.  (With the SLP vectoriser on - csrc/Makefile - the gain ended at N = 8.)
-#ifndef RC_MIXED_MAX_N
-#define RC_MIXED_MAX_N 13
-#endif
+constexpr int kMixedMaxN = 13;
 // Split tolerance of the fp32 QL.  Looser than fp32 rounding on purpose: what a dropped e_l costs (e_l^2 / gap) is
 // taken out again by the Halley step, and the step's own size is the acceptance test.  Measured (N = 7, VALU
 // instructions per wave / kernel time): 2e-6: 1750 / 60.5 us, 1e-5: 1703, 3e-5: 1678 / 58.7, 1e-4: 1627 / 58.0,
 // 3e-4: first tiles on the general path, 1e-3: 71 us.
-#ifndef RC_F32_EPS
-#define RC_F32_EPS 1e-4f
-#endif
-constexpr float kF32SplitTol = RC_F32_EPS;       // fp32 QL: e_l negligible below this * (|d_l| + |d_l+1|)
-#ifndef RC_HALLEY_ACCEPT
-#define RC_HALLEY_ACCEPT 1e-14
-#endif
-constexpr double kHalleyAccept = RC_HALLEY_ACCEPT;   // accept when max|step|^3 <= this * mingap^2 (error bound of the step)
+constexpr float kF32SplitTol = 1e-4f;            // fp32 QL: e_l negligible below this * (|d_l| + |d_l+1|)
+constexpr double kHalleyAccept = 1e-14;          // accept when max|step|^3 <= this * mingap^2 (error bound of the step)
 
 RC_HD float seed_rsqf(float x) {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -396,7 +358,7 @@ RC_HD bool tridiag_ql2_fast(TriEig<N, R>& s, const double tol_values = kFastEpsV
     const lanemask_t full = lane_ballot(true);
 #pragma unroll
     for (int l = 0; l < N - 1; ++l) {
-        if (kClosedForm2x2 && l == N - 2) {
+        if (l == N - 2) {
             // last 2x2 block [[a, e], [e, b]] in closed form (one Jacobi rotation): eigenvalues a - t, b + t with
             // t = e tau, tau = e / (delta + sign(delta) rho), delta = (b - a)/2, rho = sqrt(delta^2 + e^2); the 1e-300
             // keeps the denominator nonzero when e = delta = 0 (then t = tau = 0).
@@ -442,20 +404,11 @@ RC_HD bool tridiag_ql2_fast(TriEig<N, R>& s, const double tol_values = kFastEpsV
             // for a converged lane whose e_l and delta are both exactly zero.
             const double el = s.e[l];
             const double delta = 0.5 * (s.d[l + 1] - s.d[l]);
-#if RC_SHIFT_NODIV
             const double rho = sqrt_fast(fma(delta, delta, fma(el, el, 1e-300)));     // the nudge rides in the fma
-#else
-            const double e2 = el * el;
-            const double rho = sqrt_fast(fma(delta, delta, e2) + 1e-300);
-#endif
-#if RC_SHIFT_NODIV
             // e^2 / (delta + sign(delta) rho) = sign(delta) (rho - |delta|): no reciprocal.  The cancellation costs
             // nothing that matters: the shift then carries the seed's 5e-8 relative to rho instead of to the
             // correction, which still contracts e_l by ~1e-7 per sweep once it is small (host emulation: +1 % rotations).
             double g = s.d[N - 1] - s.d[l] + copysign(rho - fabs(delta), delta);
-#else
-            double g = s.d[N - 1] - s.d[l] + e2 * rcp_fast(delta + copysign(rho, delta));
-#endif
             double sn = 1.0, cs = 1.0, p = 0.0;
 #pragma unroll
             for (int i = N - 2; i >= l; --i) {
@@ -573,12 +526,9 @@ RC_HD bool tridiag_ql_f32(float (&d)[N], float (&e)[N], float& scale_out) {
 // |chi chi''/2| is not small against chi'^2, i.e. |p q| / (p'^2 - p q) is O(1) where a start inside the basin of a root
 // has ~ step * sum_j 1/(mu - lam_j) << 1.  `crit` returns max_k |p q / den|; callers treat crit > kHalleyCritical as "not
 // converged, keep stepping" whatever the step sizes say (1 multiplication + 1 max per eigenvalue).
-// `roots` (stepping path only, SELECT = true): bit k set = this lane wants eigenvalue k stepped; an eigenvalue no lane of
-// the tile wants is skipped wave-uniformly (typically ONE lane of a flagged tile has ONE close pair: 2 of the N chains run).
-#ifndef RC_HALLEY_CRITICAL
-#define RC_HALLEY_CRITICAL 0.2
-#endif
-constexpr double kHalleyCritical = RC_HALLEY_CRITICAL;
+// `roots`: bit k set = this lane wants eigenvalue k stepped; an eigenvalue no lane of the tile wants is skipped
+// wave-uniformly (typically ONE lane of a flagged tile has ONE close pair: 2 of the N chains run).
+constexpr double kHalleyCritical = 0.2;
 // The polynomial whose roots are wanted, as a functor: eval(mu) -> chi, chi', chi''/2; trace() = sum of the roots.
 // ChainChi: det(mu I - T) of the real symmetric tridiagonal (d0, SQUARED couplings e0sq), three-term recurrences.
 template <int N>
@@ -627,15 +577,15 @@ struct ChainChi {
     }
 };
 
-template <int N, bool SELECT = false, typename Chi>
-RC_HD double halley_polish(const Chi& chi, double (&lam)[N], double& crit, unsigned roots = ~0u) {
+template <int N, typename Chi>
+RC_HD double halley_polish(const Chi& chi, double (&lam)[N], double& crit, unsigned roots) {
     double maxd = 0.0, maxc = 0.0;
     double rest = chi.trace();                     // trace - sum of the polished eigenvalues
     // N - 1 eigenvalues are polished; the last one is what the trace leaves (2N additions instead of 7N operations;
     // it inherits the summed error of the others, ~N 1e-14)
 #pragma unroll
     for (int k = 0; k < N - 1; ++k) {
-        if (SELECT && !vote_any((roots >> k) & 1u)) {
+        if (!vote_any((roots >> k) & 1u)) {
             rest -= lam[k];
             continue;
         }
@@ -693,62 +643,20 @@ RC_HD double aberth_polish(const Chi& chi, const float (&S)[N], double (&lam)[N]
     crit = maxc;
     return maxd;
 }
-#ifndef RC_ABERTH_FIRST
-#define RC_ABERTH_FIRST 1
-#endif
-constexpr bool kAberthFirst = RC_ABERTH_FIRST;
-
-// A NEWTON step for every eigenvalue (chi, chi' only: 5 fp64 operations per (eigenvalue, site)), all N - 1 recurrence chains
-// independent of each other - the scheduler interleaves them, where the stepping loop's SELECTed Halley chains are separated by
-// wave-uniform branches and each runs at the dependent-issue rate.  The SECOND step of a tile that failed the one-step
-// acceptance (round 5, RC_STEP2_NEWTON_ALL): after the Aberth step a flagged eigenvalue is ~step^3 (N-1)/gap^2 from its root,
-// Newton's quadratic convergence finishes it: a step s from inside the basin leaves ~ s^2 sum_j 1/|lam_k - lam_j| <=
-// s^2 (N-1)/gap.  A step that is not small (or not finite) is NOT taken - the iterate stays what it was for the stepping loop
-// behind - and reported as 1e300.  Returns max_k |step_k| (the last eigenvalue: what the trace moves it by).
-template <int N, typename Chi>
-RC_HD double newton_polish_all(const Chi& chi, double (&lam)[N], double take_below) {
-    double maxd = 0.0;
-    double rest = chi.trace();
-#pragma unroll
-    for (int k = 0; k < N - 1; ++k) {
-        const double mu = lam[k];
-        double p, dp;
-        chi.eval2(mu, p, dp);
-        double y = seed_rcp(dp);
-        y = fma(y, fma(-dp, y, 1.0), y);
-        const double step = p * y;
-        const bool take = fabs(step) <= take_below;            // (false for NaN / inf)
-        lam[k] = take ? mu - step : mu;
-        rest -= lam[k];
-        maxd = fmax(maxd, take ? fabs(step) : 1e300);
-    }
-    maxd = fmax(maxd, fabs(rest - lam[N - 1]));
-    lam[N - 1] = rest;
-    return maxd;
-}
-#ifndef RC_STEP2_NEWTON_ALL
-#define RC_STEP2_NEWTON_ALL 0
-#endif
-#ifndef RC_STEP_ALL_FIRST
-#define RC_STEP_ALL_FIRST 0
-#endif
 
 // Mixed-precision eigenvalues, the fp64 half: from fp32 starting values `start` (the fp32 QL's eigenvalues, ~1e-6 of the
 // spectral scale; `ok32` = false when that QL hit its sweep cap: the starts are then arbitrary) to the eigenvalues of the
 // polynomial `chi` (ChainChi: the fp64 tridiagonal (d0, e0sq); RingChi, hermitian_core.h: the ring) at rounding level in `lam`.  Returns true when `lam` is settled; false - per lane - when the
 // caller must escalate (all-fp64 QL for the tile).  `scale32` = max(|d|, |e|) of the matrix (fp32 QL's by-product): the
 // fp32 uncertainty of a computed gap is kGapUlps32 * FLT_EPSILON * scale32 (= 4.3e-6 at the benchmark's scale of ~12).
-//   1. ONE Halley step per eigenvalue; accepted when  max|step|^3 <= kHalleyAccept * (g32 - uncertainty)^2  (the error
-//      bound of a Halley step, ~ step^3 / gap^2, g32 = smallest gap of the fp32 spectrum) AND no start sat next to a
+//   1. ONE Ehrlich-Aberth step per eigenvalue (aberth_polish); accepted when  max|step|^3 <= kHalleyAccept * (g32 - uncertainty)^2
+//      (the error bound of the step, ~ step^3 / gap^2, g32 = smallest gap of the fp32 spectrum) AND no start sat next to a
 //      critical point of chi (`crit`, see halley_polish).
 //   2. otherwise (wave-uniform: the whole tile) the flagged eigenvalues keep stepping until the step itself is <= 1e-9
 //      and off the critical points - the iterate before a tiny step was converged (error after a step of 1e-9:
 //      1e-27 / gap^2) -, up to 12 steps; then the fp64 gaps are checked so that no two starts fell into the same
 //      eigenvalue (closer than 4e-6 of the scale).
 // `extra_steps` (diagnostic, optional) is set when the tile left the one-step path.
-#ifndef RC_ALWAYS_DISTINCT_CHECK
-#define RC_ALWAYS_DISTINCT_CHECK 0
-#endif
 constexpr float kGapUlps32 = 3.0f;
 template <int N, typename Chi>
 RC_HD bool mixed_refine(const Chi& chi, const float (&start)[N], float scale32, bool ok32,
@@ -765,78 +673,25 @@ RC_HD bool mixed_refine(const Chi& chi, const float (&start)[N], float scale32, 
         for (int m = k + 1; m < N; ++m) {
             const float diff = start[k] - start[m];
             g32 = fminf(g32, fabsf(diff));
-            if (kAberthFirst) {
-                const float r = seed_rcpf(diff);
-                S[k] += r;
-                S[m] -= r;
-            }
+            const float r = seed_rcpf(diff);
+            S[k] += r;
+            S[m] -= r;
         }
     }
     const float g32c = fmaxf(g32 - unc, 0.0f);            // less the fp32 uncertainty of a difference
     const double gap2 = kHalleyAccept * ((double)g32c * (double)g32c);
 #pragma unroll
     for (int k = 0; k < N; ++k) lam[k] = (double)start[k];
+    // two starts closer than the fp32 uncertainty (possibly equal: 1/0): the sums mean nothing and the sample is not
+    // accepted whatever the step says (gap2 = 0) - a plain Newton step keeps its iterate finite for the stepping path
+    const bool sep = g32c > 0.0f;
+#pragma unroll
+    for (int k = 0; k < N; ++k) S[k] = sep ? S[k] : 0.0f;
     double crit;
-    double maxd;
-    if (kAberthFirst) {
-        // two starts closer than the fp32 uncertainty (possibly equal: 1/0): the sums mean nothing and the sample is not
-        // accepted whatever the step says (gap2 = 0) - a plain Newton step keeps its iterate finite for the stepping path
-        const bool sep = g32c > 0.0f;
-#pragma unroll
-        for (int k = 0; k < N; ++k) S[k] = sep ? S[k] : 0.0f;
-        maxd = aberth_polish<N>(chi, S, lam, crit);
-    } else {
-        maxd = halley_polish<N>(chi, lam, crit);
-    }
+    double maxd = aberth_polish<N>(chi, S, lam, crit);
     bool need = !(maxd * maxd * maxd <= gap2) || !(crit <= kHalleyCritical) || !ok32;
-#ifdef RC_EXPERIMENT_NO_STEPPING
-    // TIMING EXPERIMENT ONLY (scripts/build_variant.sh nostep; results of flagged samples are wrong): the kernel without its
-    // stepping path = the most that deferring flagged samples to a second launch could save
-    return true;
-#endif
-    if (RC_LIKELY(!vote_any(need))) return true;
-#if defined(RC_EXPERIMENT_STEP_NOT_RUN) && defined(__HIP_DEVICE_COMPILE__)
-    {   // TIMING EXPERIMENT ONLY: the stepping path (and everything behind it) compiled in but never executed - an opaque
-        // always-true flag the optimiser cannot see through; separates what the code's PRESENCE costs from what running it costs
-        int never = 1;
-        asm volatile("" : "+s"(never));
-        if (never) return true;
-    }
-#endif
+    if (!vote_any(need)) return true;
     if (extra_steps) *extra_steps = 1;
-#if RC_STEP2_NEWTON_ALL
-    {
-        // (round 5) Before any bookkeeping: ONE Newton step for every eigenvalue of every lane, chains interleaved.  Accepted -
-        // wave-wide - when (N-1) s^2 <= kHalleyAccept (g32 - uncertainty) for the largest step s of the sample (error after a
-        // Newton step from inside the basin: s^2 sum_j 1/|lam_k - lam_j| <= s^2 (N-1)/gap; s <= 1e-7 sqrt(gap/(N-1)) also puts
-        // the iterate N s << gap from its root - |chi'/chi| <= N / min_j|mu - lam_j| - so the root it converged to is isolated),
-        // the first step was off the critical points and the fp32 QL had converged.  Otherwise the iterates - improved where the
-        // step was small, untouched where it was not - go on into the stepping loop below as before.
-        const double maxd2 = newton_polish_all<N>(chi, lam, 1e-3 * (double)fmaxf(scale32, 1.0f));
-        const bool ok2 = ok32 && (crit <= kHalleyCritical) && ((double)(N - 1) * maxd2 * maxd2 <= kHalleyAccept * (double)g32c);
-        if (!vote_any(!ok2)) {
-            if (extra_steps) *extra_steps = 100;           // (diagnostic: settled by the all-eigenvalue Newton step)
-            float moved2 = 0.0f;
-#pragma unroll
-            for (int k = 0; k < N; ++k) moved2 = fmaxf(moved2, (float)fabs((double)start[k] - lam[k]));
-            const float res2 = 4e-6f * fmaxf(scale32, 1.0f);
-            bool dup = false;
-            if (RC_ALWAYS_DISTINCT_CHECK || vote_any(!(g32 > 2.0f * moved2 + res2))) {
-                float lf2[N], mingap2 = 1e30f;
-#pragma unroll
-                for (int k = 0; k < N; ++k) lf2[k] = (float)lam[k];
-#pragma unroll
-                for (int k = 0; k < N; ++k) {
-#pragma unroll
-                    for (int m = k + 1; m < N; ++m) mingap2 = fminf(mingap2, fabsf(lf2[k] - lf2[m]));
-                }
-                dup = !(mingap2 > res2);
-            }
-            return !dup;
-        }
-        maxd = fmin(maxd, 1e10);       // (the bookkeeping below reads the FIRST step's size: unchanged)
-    }
-#endif
     // Rare per sample, not per tile (close pair or a poor fp32 start somewhere among the 64): which eigenvalues - the step
     // bound again, per eigenvalue, with ITS gap to the nearest other one and (round 4) ITS OWN step: what the first step
     // leaves of eigenvalue k's error is own_k^2 * (largest error among the other starts) * (N-1) / gap_k^2 (Aberth: the
@@ -847,23 +702,7 @@ RC_HD bool mixed_refine(const Chi& chi, const float (&start)[N], float scale32, 
     // fp32 QL failed, or with a start at a critical point, wants all of them.
     unsigned roots = 0u;
     float moved = 0.0f;                                   // largest |start_k - lam_k| of this sample so far
-    bool settled = false;
-    const double maxd1 = maxd;                            // the FIRST step's size: what the bookkeeping's error estimate is written in
-#if RC_STEP_ALL_FIRST
     {
-        // (round 5 experiment) the first stepping iteration for EVERY eigenvalue - N - 1 independent Halley chains the scheduler can
-        // interleave, where the SELECTed chains below run one after the other behind wave-uniform branches - and no bookkeeping
-        // unless a second iteration is needed (83 % of the flagged tiles need one)
-#pragma unroll
-        for (int k = 0; k < N; ++k) moved = fmaxf(moved, (float)fabs((double)start[k] - lam[k]));
-        maxd = halley_polish<N>(chi, lam, crit);
-        moved += (float)fmin(maxd, 1e10);
-        need = !(maxd <= 1e-9) || !(crit <= kHalleyCritical);
-        if (extra_steps) *extra_steps = 2;
-        settled = !vote_any(need);
-    }
-#endif
-    if (!settled) {
         float lf[N];
 #pragma unroll
         for (int k = 0; k < N; ++k) lf[k] = (float)lam[k];
@@ -879,7 +718,7 @@ RC_HD bool mixed_refine(const Chi& chi, const float (&start)[N], float scale32, 
                 gk[m] = fminf(gk[m], df);
             }
         }
-        const float mx = (float)fmin(maxd1, 1e10);
+        const float mx = (float)fmin(maxd, 1e10);          // the FIRST step's size: what the error estimate is written in
         const bool all = !ok32 || !(crit <= kHalleyCritical);
 #pragma unroll
         for (int k = 0; k < N; ++k) {
@@ -895,8 +734,8 @@ RC_HD bool mixed_refine(const Chi& chi, const float (&start)[N], float scale32, 
     rc_flag_stats_hook(N, roots, maxd, lam);              // (scripts/proto/flag_stats.cpp: host-side statistics of the stepping path)
 #endif
 #pragma unroll 1
-    for (int it = 0; it < 12 && !settled; ++it) {         // (settled: wave-uniform)
-        maxd = halley_polish<N, true>(chi, lam, crit, roots);
+    for (int it = 0; it < 12; ++it) {
+        maxd = halley_polish<N>(chi, lam, crit, roots);
         moved += (float)fmin(maxd, 1e10);
         need = !(maxd <= 1e-9) || !(crit <= kHalleyCritical);
         if (extra_steps) *extra_steps = 2 + it;           // (diagnostic: 1 + stepping iterations executed)
@@ -906,7 +745,7 @@ RC_HD bool mixed_refine(const Chi& chi, const float (&start)[N], float scale32, 
     // than ~4e-6 of the scale go to the all-fp64 QL.  Skipped - wave-uniformly - when it cannot fail: every iterate ended
     // within `moved` of its start, so with the smallest START gap above 2 moved + the resolution no two of them coincide.
     const float res = 4e-6f * fmaxf(scale32, 1.0f);
-    if (RC_ALWAYS_DISTINCT_CHECK || vote_any(!(g32 > 2.0f * moved + res))) {
+    if (vote_any(!(g32 > 2.0f * moved + res))) {
         float lf[N], mingap = 1e30f;
 #pragma unroll
         for (int k = 0; k < N; ++k) lf[k] = (float)lam[k];
@@ -1049,7 +888,7 @@ RC_HD bool ends_weights(double pe, const double (&lam)[N], double (&w)[N], doubl
         }
     }
     bool ok = !GAPS || mingap > gap_tol * scale;
-    if (kBatchInverse && N >= 3 && N <= 13) {         // (above: the prefix arrays cost registers the N >= 14 kernels lack)
+    if (N >= 3 && N <= 13) {        // (above: the prefix arrays cost registers the N >= 14 kernels lack)
         // One reciprocal per BATCH of weights (prefix products, invert the total, peel off): 3(B-1) multiplications + 1
         // reciprocal instead of B reciprocals (a v_rcp_f64 costs 3.4 FMAs, its refinement 5 more).  A batch total is a
         // product of B (N-1) eigenvalue differences, at most (2 scale)^(B (N-1)); B is chosen so that B (N-1) <= 60
@@ -1096,10 +935,7 @@ RC_HD bool ends_weights(double pe, const double (&lam)[N], double (&w)[N], doubl
 // guard on each total; N = 2 and N >= 14: one reciprocal per eigenvalue, as there.
 // A product of squares that underflowed to 0 (several cut bonds) gives F = 0; a sum that is not finite gives a NaN, which
 // the caller's `fid <= 2` sends to the repair route.  `lam`, GAPS, `gap_tol`: as for ends_weights; T: the time (>= 0).
-#ifndef RC_ENDS_AMPLITUDE_MAX_N
-#define RC_ENDS_AMPLITUDE_MAX_N 13
-#endif
-constexpr int kEndsAmplitudeMaxN = RC_ENDS_AMPLITUDE_MAX_N;   // REGISTER limit of the kernels (nothing to do with RC_MIXED_MAX_N): see chain_fidelity_fast
+constexpr int kEndsAmplitudeMaxN = 13;   // REGISTER limit of the kernels (nothing to do with kMixedMaxN): see chain_fidelity_fast
 template <int N, bool GAPS>
 RC_HD bool ends_amplitude(double pe_sq, const double (&lam)[N], double T, const double* sctab, double& fid,
                           double gap_tol = kDegenerateGapNoMix) {
@@ -1119,7 +955,7 @@ RC_HD bool ends_amplitude(double pe_sq, const double (&lam)[N], double T, const 
         }
     }
     bool ok = !GAPS || mingap > gap_tol * scale;
-    constexpr bool BATCH = kBatchInverse && N >= 3 && N <= 13;
+    constexpr bool BATCH = N >= 3 && N <= 13;
     constexpr int B = !BATCH ? N : ((60 / (N - 1)) < 1 ? 1 : (60 / (N - 1)));      // (not batched: one "batch" with total 1)
     constexpr int NB = (N + B - 1) / B;
     double rinv[NB];
@@ -1162,8 +998,7 @@ RC_HD bool ends_amplitude(double pe_sq, const double (&lam)[N], double T, const 
                 continue;
             }
             double sk, ck;
-            if (kTableSinCos) sincos_table(Tk * (lam[k] - lam[0]), sctab, sk, ck);
-            else sincos_reduced(T * (lam[k] - lam[0]), sk, ck);
+            sincos_table(Tk * (lam[k] - lam[0]), sctab, sk, ck);
             reb = (k == k0) ? w[k] * ck : fma(w[k], ck, reb);
             imb = (k == k0 || k == 1) ? w[k] * sk : fma(w[k], sk, imb);
         }
@@ -1200,10 +1035,7 @@ RC_HD bool ends_amplitude(double pe_sq, const double (&lam)[N], double T, const 
 #define RC_SUM_RULE_GUARD 1
 #endif
 constexpr bool kSumRuleGuard = RC_SUM_RULE_GUARD;
-#ifndef RC_SUM_RULE_TOL
-#define RC_SUM_RULE_TOL 2e-12
-#endif
-constexpr double kSumRuleTol = RC_SUM_RULE_TOL;     // |moment residual| <= tol * (2 scale)^m
+constexpr double kSumRuleTol = 2e-12;               // |moment residual| <= tol * (2 scale)^m
 // How many of the three rules are evaluated (1 = m = 0 only).  m = 0 alone already sees the failure the guard exists for:
 // independent noise e_a, e_b on the two weights of a close pair shows up as e_a + e_b; the component it cannot see
 // (e_a = -e_b) changes the amplitude by e_a (exp(-i T lam_a) - exp(-i T lam_b)) ~ e_a T gap - harmless exactly where the
@@ -1221,11 +1053,7 @@ constexpr int kSumRuleMoments = RC_SUM_RULE_MOMENTS;
 // Lagrange's identity sum_k lam_k^m / chi'(lam_k) = 0 - true for ANY set of distinct lam_k up to the rounding of the
 // products themselves (1e-16 relative): there is no recurrence noise to catch.  (What such a check would cost the headline
 // kernel read +3.3 % in the first A/B and -0.1 % in the second, profiles/r04_ab_guard.txt - inside the box-to-box noise; it
-// stays off because it cannot fail, not because of its price.)
-#ifndef RC_SUM_RULE_ENDS
-#define RC_SUM_RULE_ENDS 0
-#endif
-constexpr bool kSumRuleEnds = RC_SUM_RULE_ENDS;
+// is not built because it cannot fail, not because of its price.)
 
 // d[idx] for a wave-uniform runtime index WITHOUT dynamic register indexing: a chain of selects on array elements is turned
 // into a load from a selected address by the optimiser - the array then lives in scratch memory (measured: 16 N bytes of
@@ -1313,7 +1141,7 @@ enum WeightMode {
 // Fidelity of one sample - fast path.  loadg(j) returns this sample's j-th draw, laid out (g0_i, g1_i, g2_i),
 // i = 0..N-1.  x: controller (N biases, then T); sctab: the sin/cos table (RC_SINCOS_TABLE_VALUES).  Returns false -
 // per sample - when this sample needs the general path.
-// Eigenvalues: the eigenvalue-only modes at 3 <= N <= RC_MIXED_MAX_N take the mixed-precision route (fp32 QL -> fp64 Halley
+// Eigenvalues: the eigenvalue-only modes at 3 <= N <= kMixedMaxN take the mixed-precision route (fp32 QL -> fp64 Aberth
 // step -> stepping path -> all-fp64 QL for the tile, in that order of escalation; see the block comment at kMixedEig);
 // the rows mode and larger N run the all-fp64 QL (tridiag_ql2_fast).
 // AMPLITUDE = false keeps the end-to-end mode on the weights (the directional kernel: see there).
@@ -1324,12 +1152,12 @@ RC_HD bool chain_fidelity_fast(const double* x, const double* h0d, const double*
                                int in, int out, const double* sctab, double& fid, long long* stamp = nullptr,
                                int* extra_steps = nullptr) {
     constexpr bool VEC = (MODE == kWeightsRows);
-    constexpr bool MIXED = kMixedEig && !VEC && N >= 3 && N <= RC_MIXED_MAX_N;
+    constexpr bool MIXED = kMixedEig && !VEC && N >= 3 && N <= kMixedMaxN;
     // end-to-end mode: the fidelity straight from the eigenvalues and the product of the SQUARED couplings (ends_amplitude).
-    // The weights are formed as before (ends_weights, pe = the root of that product) where the sum-rule guard is switched on
-    // for this mode - it reads them -, at N >= 14 - with ends_amplitude the N = 14 kernel spills 6 registers and the N = 14
-    // fused-draws kernel goes from 244 to 264, a wave of residency - and for a caller that asks for it (AMPLITUDE = false).
-    constexpr bool AMP = AMPLITUDE && (MODE == kWeightsEnds) && !kSumRuleEnds && N <= kEndsAmplitudeMaxN;
+    // The weights are formed as before (ends_weights, pe = the root of that product) at N >= 14 - with ends_amplitude
+    // the N = 14 kernel spills 6 registers and the N = 14 fused-draws kernel goes from 244 to 264, a wave of residency - and
+    // for a caller that asks for it (AMPLITUDE = false).
+    constexpr bool AMP = AMPLITUDE && (MODE == kWeightsEnds) && N <= kEndsAmplitudeMaxN;
     TriEig<N, VEC ? 2 : 0> s;
     double d0[N], e0sq[N], w[N];               // kWeightsAdjugate / mixed path: original diagonal / squared couplings
     float df[N], ef[N];                        // mixed path: the fp32 copy the QL rotations work on
@@ -1399,14 +1227,7 @@ RC_HD bool chain_fidelity_fast(const double* x, const double* h0d, const double*
         ok = true;
         const ChainChi<N> chi{d0, e0sq};
         bool need = !mixed_refine<N>(chi, df, scale32, ok32, s.d, extra_steps);
-#if defined(RC_EXPERIMENT_FALLBACK_NOT_RUN) && defined(__HIP_DEVICE_COMPILE__)
-        {   // TIMING EXPERIMENT ONLY: the tile-wide all-fp64 QL compiled in but never executed (results of such tiles are wrong)
-            int never = 1;
-            asm volatile("" : "+s"(never));
-            if (never) need = false;
-        }
-#endif
-        if (RC_UNLIKELY(vote_any(need))) {
+        if (vote_any(need)) {
             // still not settled somewhere in the tile (a pair closer than ~5e-5: beyond what a polynomial iteration
             // from an fp32 start separates): the whole tile takes the all-fp64 QL from the original matrix, wave-wide
             // (~2x the cost of this tile), with the TIGHT split tolerance (the 1e-10 of the eigenvalue-only fast path
@@ -1457,25 +1278,9 @@ RC_HD bool chain_fidelity_fast(const double* x, const double* h0d, const double*
             e0sq[N - 1] = 0.0;
         }
         ok = tridiag_ql2_fast(s);                   // per lane; a bad lane just keeps computing garbage
-        // (round 4) N >= 14, general adjugate mode: ONE Halley step on chi of the original matrix takes the QL's eigenvalues
-        // (error ~N eps scale: at |d| ~ 100, |T| ~ 100, N = 16 a phase error of 3e-11 - the fuzz campaign's worst chain
-        // cases once the mixed path's were gone) to a few ulp.  d0 / e0sq are alive in this mode anyway (the weights'
-        // recurrences); the end-to-end mode at these sizes has no register for them and keeps the QL's values.  A lane
-        // whose step is not tiny (a pair the gap test below rejects anyway, or a non-converged QL) keeps what it had.
-        if (kPolishLargeN && MODE == kWeightsAdjugate && N > RC_MIXED_MAX_N) {
-            double lam[N];
-#pragma unroll
-            for (int i = 0; i < N; ++i) lam[i] = s.d[i];
-            double crit;
-            const ChainChi<N> chi{d0, e0sq};
-            const double maxd = halley_polish<N>(chi, lam, crit);
-            double scale = 1.0;
-#pragma unroll
-            for (int i = 0; i < N; ++i) scale = fmax(scale, fabs(s.d[i]));
-            const bool take = (maxd <= 1e-9 * scale) && (crit <= kHalleyCritical);
-#pragma unroll
-            for (int i = 0; i < N; ++i) s.d[i] = take ? lam[i] : s.d[i];
-        }
+        // (One Halley step on chi of the original matrix behind this QL at N >= 14, general adjugate mode, took the fuzz block's
+        // N = 16 worst case from 1.03e-11 to 6.4e-12 for +16 % kernel time at N = 14 and 16, while the campaign's overall worst,
+        // 1.1e-11, is set elsewhere: profiles/r04_ab_polish_large_n.txt.  Not kept.)
     }
 #if defined(RC_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
     __builtin_amdgcn_sched_barrier(0);
@@ -1502,8 +1307,7 @@ RC_HD bool chain_fidelity_fast(const double* x, const double* h0d, const double*
 #pragma unroll
         for (int k = 1; k < N; ++k) {
             double sk, ck;
-            if (kTableSinCos) sincos_table(Tk * (s.d[k] - s.d[0]), sctab, sk, ck);
-            else sincos_reduced(T * (s.d[k] - s.d[0]), sk, ck);
+            sincos_table(Tk * (s.d[k] - s.d[0]), sctab, sk, ck);
             re = fma(w[k], ck, re);
             im = fma(-w[k], sk, im);
         }
@@ -1511,7 +1315,7 @@ RC_HD bool chain_fidelity_fast(const double* x, const double* h0d, const double*
     }
     if (MIXED || AMP) ok = ok && (fid <= 2.0);      // a NaN (zero Halley denominator, sums out of range) goes to the general path
     // (the rows mode carries genuine eigenvector rows: it IS the repair route and needs no guard)
-    if (kSumRuleGuard && !VEC && (MODE != kWeightsEnds || kSumRuleEnds))
+    if (kSumRuleGuard && !VEC && MODE != kWeightsEnds)
         ok = ok && chain_sum_rules_ok<N, MODE == kWeightsEnds>(w, s.d, hi - lo, gsites, pe_all, MIXED ? (double)scale32 : 0.0);
     return ok;
 }

@@ -101,8 +101,9 @@ int rc_device_count(void);
 const char* rc_last_error(void);
 
 /* (ABI 6) Compile-time switches of THIS build that change results or remove a safety net; 0 = the product build.  The
- * RC_BUILD_EXPERIMENT_* builds (scripts/build_variant.sh: timing experiments) knowingly return wrong fidelities for some
- * samples - a loader must refuse them (code-robchar_amd/_lib.py does, unless ROBCHAR_ALLOW_EXPERIMENT_LIB=1). */
+ * four RC_BUILD_EXPERIMENT_* bits are RESERVED: no switch of this tree sets them; only timing-experiment builds of earlier trees
+ * do, and those knowingly return wrong fidelities for some samples - a loader must go on refusing them (code-robchar_amd/_lib.py
+ * does, unless ROBCHAR_ALLOW_EXPERIMENT_LIB=1). */
 #define RC_BUILD_EXPERIMENT_NO_STEPPING 1
 #define RC_BUILD_EXPERIMENT_STEP_NOT_RUN 2
 #define RC_BUILD_EXPERIMENT_FALLBACK_NOT_RUN 4

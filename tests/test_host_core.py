@@ -774,15 +774,14 @@ def wave(tmp_path_factory):
     the QL's eigenvalues (-DRC_KEEP_SETTLED=0: the behaviour before round 4)."""
     d = tmp_path_factory.mktemp("hostwave")
     libs = {}
-    for name, flags in (("new", []), ("old", ["-DRC_KEEP_SETTLED=0"]), ("newton", ["-DRC_STEP2_NEWTON_ALL=1"]),
-                        ("allfirst", ["-DRC_STEP_ALL_FIRST=1"])):
+    for name, flags in (("new", []), ("old", ["-DRC_KEEP_SETTLED=0"])):
         out = d / f"librc_hostwave_{name}.so"
         subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-shared", "-fPIC", "-pthread"] + flags
                        + ["-o", str(out), os.path.join(ROOT, "tests", "host", "host_wave.cpp")], check=True)
         libs[name] = ctypes.CDLL(str(out))
     PI = ctypes.POINTER(ctypes.c_int)
 
-    def tile(ctrl, draws, N, a, b, mode=None, h0d=None, old=False, variant=None):
+    def tile(ctrl, draws, N, a, b, mode=None, h0d=None, old=False):
         ctrl = np.ascontiguousarray(ctrl, dtype=np.float64).reshape(-1)
         draws = np.ascontiguousarray(draws, dtype=np.float64)
         nk = draws.shape[0]
@@ -793,7 +792,7 @@ def wave(tmp_path_factory):
         if mode is None:
             mode = 2 if {a, b} == {0, N - 1} else 1
         fid, rep, ex = np.empty(nk), np.zeros(nk, dtype=np.int32), np.zeros(nk, dtype=np.int32)
-        rc = libs[variant or ("old" if old else "new")].rc_host_wave_chain_tile(
+        rc = libs["old" if old else "new"].rc_host_wave_chain_tile(
             N, ctrl.ctypes.data_as(P), h0.ctypes.data_as(P), h0o.ctypes.data_as(P), draws.ctypes.data_as(P), nk, a, b, mode,
             fid.ctypes.data_as(P), rep.ctypes.data_as(PI), ex.ctypes.data_as(PI))
         assert rc == 0
@@ -874,30 +873,23 @@ def test_wave_emulation_random_tiles_vs_oracle(wave, N):
 
 
 @pytest.mark.parametrize("cid", [3, 5])
-def test_wave_emulation_second_step_newton_for_all_eigenvalues(wave, cid):
-    """-DRC_STEP2_NEWTON_ALL=1 (round 5 experiment, tridiag_core.h: newton_polish_all): a tile that fails the one-step
-    acceptance takes ONE Newton step for every eigenvalue (independent chains) before any bookkeeping and is accepted on
-    (N-1) s^2 <= 1e-14 gap.  In lock-step on the DELOCALISED controller sets (close pairs by construction: mirror-symmetric
-    shipped L-BFGS controllers, N = 7; constructed N = 10 XXZ) against the oracle: same 1e-11 as the shipped route, and the
-    Newton step does settle most of the tiles that left the one-step path (otherwise the variant has no point)."""
+def test_wave_emulation_delocalised_controllers_vs_oracle(wave, cid):
+    """The shipped route in lock-step on the DELOCALISED controller sets (close pairs by construction: mirror-symmetric shipped
+    L-BFGS controllers, N = 7; constructed N = 10 XXZ) against the oracle: 1e-11, and the inputs do drive tiles off the one-step
+    path of the mixed-precision route (the stepping path is what the test is about)."""
     from conftest import highfid_workload
     N, a, b, ctrl, h0 = highfid_workload(cid, 24)
     rng = np.random.default_rng(1700 + cid)
-    stats = {"flagged": 0, "newton": 0, "tiles": 0}
-    worst = {"new": 0.0, "newton": 0.0}
+    flagged, worst = 0, 0.0
     for c in range(24):
         g = 0.05 * rng.standard_normal((64, N, 3))
         want = orc.fidelity_eigh(ctrl[c:c + 1], g[None], N, a, b, h0_diag=h0)[0]
-        for variant in ("new", "newton", "allfirst"):
-            fid, rep, ex = wave(ctrl[c], g, N, a, b, h0d=h0, variant=variant)
-            worst[variant] = max(worst.get(variant, 0.0), float(np.abs(fid - want).max()))
-            if variant == "newton":
-                stats["tiles"] += 1
-                stats["flagged"] += int((ex > 0).any())
-                stats["newton"] += int((ex == 100).all())
-    # (`allfirst` = -DRC_STEP_ALL_FIRST=1: the first stepping iteration for every eigenvalue, bookkeeping only behind it)
-    assert worst["new"] < 1e-11 and worst["newton"] < 1e-11 and worst["allfirst"] < 1e-11, worst
-    assert stats["flagged"] >= 3 and stats["newton"] >= 0.5 * stats["flagged"], stats
+        fid, rep, ex = wave(ctrl[c], g, N, a, b, h0d=h0)
+        worst = max(worst, float(np.abs(fid - want).max()))
+        flagged += int((ex > 0).any())
+    print(f"cid = {cid}: worst |fid - oracle| {worst:.3e}, tiles off the one-step path {flagged} of 24")
+    assert worst < 1e-11, worst
+    assert flagged >= 3, flagged
 
 
 @pytest.mark.parametrize("N", [3, 4, 6, 7, 9, 10])
