@@ -41,6 +41,10 @@
  *   h0_diag     [N] or NULL   static diagonal added to every sample (NULL = 0; the XXZ term of
  *                             qnewton.py:148-150 goes here).  HOST pointer.
  *   h0_offdiag  [N-1] or NULL static couplings (NULL = 1.0, noise_model.py:80-82).  HOST pointer.
+ *
+ * Alignment of device pointers: that of the element type (8 bytes for fp64 and 64-bit integers, 4 for int32) and nothing
+ * more - an array may start at any element of a larger allocation.  Where an array sits changes no result (same inputs,
+ * same bits), and no entry reads or writes outside the arrays it is given (tests/test_gpu_placement.py).
  */
 #ifndef ROBCHAR_HIP_H
 #define ROBCHAR_HIP_H
