@@ -262,45 +262,7 @@ __global__ __launch_bounds__(64, fid_min_waves(N, MODE)) void mc_fid_chain_kerne
 constexpr int kRingMaxN = 16;
 constexpr int ring_min_waves(int n) { return n <= 4 ? 5 : (n <= 5 ? 4 : (n <= 6 ? 3 : (n <= 8 ? 2 : 1))); }
 
-// HBM -> LDS -> registers for one tile (see mc_fid_chain_kernel): the nk * G doubles at `src` through the `stage` buffer in
-// PH phases; lane l < nk ends with its G values in gl.
-template <int G, int PH>
-__device__ __forceinline__ void stage_tile_draws(const char* src, int nk, int lane, int align16, double* stage, double (&gl)[G]) {
-    constexpr int SP = 64 / PH;
-    constexpr int kPhaseBytes = SP * G * 8;
-#pragma unroll
-    for (int ph = 0; ph < PH; ++ph) {
-        const int first = ph * SP;
-        if (first < nk) {                          // wave-uniform
-            const int cnt = (nk - first < SP) ? (nk - first) : SP;
-            const int bytes = cnt * G * 8;
-            const char* ps = src + (long long)first * G * 8;
-            if (align16 && !(cnt & 1)) {
-#pragma unroll
-                for (int it = 0; it < (kPhaseBytes + 1023) / 1024; ++it) {
-                    const int off = it * 1024 + lane * 16;
-                    if (off < bytes)
-                        __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off), (rc_lptr_t)((char*)stage + it * 1024), 16, 0, rckp::kDrawLoadAux);
-                }
-            } else {
-#pragma unroll 2
-                for (int it = 0; it < (kPhaseBytes + 255) / 256; ++it) {
-                    const int off = it * 256 + lane * 4;
-                    if (off < bytes)
-                        __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off), (rc_lptr_t)((char*)stage + it * 256), 4, 0, rckp::kDrawLoadAux);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            int rel = lane - first;
-            asm volatile("" : "+v"(rel));                             // one base address + immediate offsets (see chain kernel)
-            if (rel >= 0 && rel < cnt) {
-#pragma unroll
-                for (int i = 0; i < G; ++i) gl[i] = stage[rel * G + i];
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        }
-    }
-}
+// (stage_tile_draws, the staging of mc_fid_chain_kernel as a function: tile_stage.inc.h)
 
 // One tile of the ring topology through the all-fp64 route (Householder with rows + QL with rows; hermitian_core.h).
 // `sctab` must have been filled; one wave.

@@ -37,7 +37,6 @@ __global__ __launch_bounds__(64, grad_min_waves(N)) void mc_fid_grad_kernel(cons
     constexpr int G = 3 * N;                       // doubles per sample
     constexpr int PH = grad_phases(N);
     constexpr int SP = 64 / PH;                    // samples per staging phase
-    constexpr int kPhaseBytes = SP * G * 8;
     constexpr int kWork = 2 * N + N * N;           // doubles per sample of the textbook routine
     constexpr int CH = (SP * G) / kWork;           // samples of it that fit the staging buffer at a time
     static_assert(CH >= 1, "staging buffer too small for the textbook routine");
@@ -71,41 +70,10 @@ __global__ __launch_bounds__(64, grad_min_waves(N)) void mc_fid_grad_kernel(cons
         return;
     }
 
-    // HBM -> LDS -> registers (see mc_fid_chain_kernel)
+    // HBM -> LDS -> registers, with the default cache policy (AUX = 0)
     const char* src = (const char*)(p.draws + c * p.draw_cstride + kb * G);
     double gl[G];
-#pragma unroll
-    for (int ph = 0; ph < PH; ++ph) {
-        const int first = ph * SP;
-        if (first < nk) {                          // wave-uniform
-            const int cnt = (nk - first < SP) ? (nk - first) : SP;
-            const int bytes = cnt * G * 8;
-            const char* ps = src + (long long)first * G * 8;
-            if (p.align16 && !(cnt & 1)) {
-#pragma unroll
-                for (int it = 0; it < (kPhaseBytes + 1023) / 1024; ++it) {
-                    const int off = it * 1024 + lane * 16;
-                    if (off < bytes)
-                        __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off), (rc_lptr_t)((char*)stage + it * 1024), 16, 0, 0);
-                }
-            } else {
-#pragma unroll 2
-                for (int it = 0; it < (kPhaseBytes + 255) / 256; ++it) {
-                    const int off = it * 256 + lane * 4;
-                    if (off < bytes)
-                        __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off), (rc_lptr_t)((char*)stage + it * 256), 4, 0, 0);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // DMA landed
-            int rel = lane - first;
-            asm volatile("" : "+v"(rel));                             // one base address + immediate offsets
-            if (rel >= 0 && rel < cnt) {
-#pragma unroll
-                for (int i = 0; i < G; ++i) gl[i] = stage[rel * G + i];
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // reads done before the buffer is refilled
-        }
-    }
+    stage_tile_draws<G, PH, 0>(src, nk, lane, p.align16, stage, gl);
     __builtin_amdgcn_s_setprio(0);
 
     constexpr int R = rc::grad_batch_rows(N);      // rows of the eigenvector matrix per QL pass (grad_core.h)

@@ -30,7 +30,6 @@ constexpr int grad_listed_min_waves(int n) { return grad_philox_min_waves(n); }
 template <int N>
 __global__ __launch_bounds__(64, grad_listed_min_waves(N)) void mc_fid_grad_listed_kernel(const GradListedParams p) {
     constexpr int G = 3 * N;                       // doubles per sample
-    constexpr int NPAIR = G / 2 + 1;               // Box-Muller pairs that cover G consecutive elements from either parity
     constexpr int kWork = 2 * N + N * N;           // doubles per sample of the textbook routine
     constexpr int CH = N <= 8 ? 8 : 4;             // lanes of it at a time
     __shared__ __attribute__((aligned(16))) double sctab[128];
@@ -39,10 +38,7 @@ __global__ __launch_bounds__(64, grad_listed_min_waves(N)) void mc_fid_grad_list
 
     const int lane = threadIdx.x;
     const long long tile = blockIdx.x;             // wave-uniform
-    reinterpret_cast<double2*>(sctab)[lane] = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-    reinterpret_cast<double2*>(lntab)[lane] = reinterpret_cast<const double2*>(g_ln_table)[lane];
-    reinterpret_cast<double2*>(lntab)[lane + 64] = reinterpret_cast<const double2*>(g_ln_table)[lane + 64];
-    __syncthreads();                               // (one wave per workgroup: no wait)
+    philox_stage_tables(lane, sctab, lntab);
     const long long c = tile / p.tiles_per_ctrl;
     const long long sb = (tile - c * p.tiles_per_ctrl) * 64;       // first slot of this tile
     const int nl = (int)((p.L - sb < 64) ? (p.L - sb) : 64);
@@ -79,22 +75,9 @@ __global__ __launch_bounds__(64, grad_listed_min_waves(N)) void mc_fid_grad_list
         const bool lv = k >= 0 && (long long)k < p.K;
         livemask = __ballot(lv);
         if (lv) {
-            // this lane's G elements start at E; the pairs (2 ctr, 2 ctr + 1) that cover them start at ctr = E >> 1
+            // this lane's G elements start at E
             const unsigned long long E = p.offset + (unsigned long long)(rowk + k) * (unsigned long long)G;
-            const unsigned long long c0 = E >> 1;
-            const bool odd = (E & 1ull) != 0ull;
-            double sn_prev = 0.0;
-#pragma unroll
-            for (int t = 0; t < NPAIR; ++t) {
-                double amp, cs, sn;
-                philox_pair(p.seed, c0 + (unsigned long long)t, sigma, lntab, sctab, amp, cs, sn);
-                // rounded products, as philox_normal_kernel stores them (opaque: never contracted into a consumer)
-                double a = amp * cs, b = amp * sn;
-                asm volatile("" : "+v"(a), "+v"(b));
-                if (2 * t < G) gl[2 * t] = odd ? b : a;
-                if (t >= 1 && 2 * t - 1 < G) gl[2 * t - 1] = odd ? a : sn_prev;
-                sn_prev = b;
-            }
+            philox_lane_draws<G>(p.seed, E, sigma, lntab, sctab, gl);
         }
     }
     const bool live = (livemask >> lane) & 1ull;

@@ -1,8 +1,7 @@
 // mc_fid_grad_philox_kernel<N> (N = 2 .. RC_MAX_NSPIN_GRAD): mc_fid_grad_kernel (k_fidelity_grad.inc.h) with the counter-based
 // draws generated WHERE THEY ARE CONSUMED, as mc_fid_sens_philox_kernel does for the noise sensitivity, plus - on request - the
 // second-moment sums from which the gradient of the row's variance follows.  No draw tensor exists: lane (c, k) makes its 3 N
-// normals with the routine philox_normal_kernel uses (philox_pair, philox_core.inc.h; NPAIR = 3N/2 + 1 pairs, every value a select
-// between neighbouring pairs, the rounded products amp * cos, amp * sin kept opaque).  Two draw modes (p.shared):
+// normals with philox_lane_draws (philox_core.inc.h: the bits philox_normal_kernel stores).  Two draw modes (p.shared):
 //     per-controller draws:  sample (c, k), site i, slot s is element  offset + ((c K + k) N + i) 3 + s  of stream `seed`;
 //     shared draws (common random numbers, the fidelity_ss_av objective):  element  offset + (k N + i) 3 + s,  the same for every c;
 // in both scaled by sigma or by the wave-uniform sigma_rows[c].
@@ -31,7 +30,7 @@ constexpr int grad_philox_min_waves(int n) { return grad_min_waves(n); }
 
 // philox_element as a CALL (22 registers of its own, no stack): inlined into the fallback its temporaries sit on top of the
 // eigenvector rows that are live there, and N = 10 .. 12 need 385 - 400 registers and 2 - 8 VGPR -> AGPR spill copies instead of
-// 362 - 382 and none.  Rare path only.
+// 360 - 380 and none.  Rare path only.
 __device__ __attribute__((noinline)) double grad_philox_element(unsigned long long seed, unsigned long long e, double scale,
                                                                 const double* lntab, const double* sctab) {
     return philox_element(seed, e, scale, lntab, sctab);
@@ -40,7 +39,6 @@ __device__ __attribute__((noinline)) double grad_philox_element(unsigned long lo
 template <int N>
 __global__ __launch_bounds__(64, grad_philox_min_waves(N)) void mc_fid_grad_philox_kernel(const GradPhiloxParams p) {
     constexpr int G = 3 * N;                       // doubles per sample
-    constexpr int NPAIR = G / 2 + 1;               // Box-Muller pairs that cover G consecutive elements from either parity
     constexpr int kWork = 2 * N + N * N;           // doubles per sample of the textbook routine
     constexpr int CH = N <= 8 ? 8 : 4;             // lanes of it at a time
     __shared__ __attribute__((aligned(16))) double sctab[128];
@@ -49,10 +47,7 @@ __global__ __launch_bounds__(64, grad_philox_min_waves(N)) void mc_fid_grad_phil
 
     const int lane = threadIdx.x;
     const long long tile = blockIdx.x;             // wave-uniform
-    reinterpret_cast<double2*>(sctab)[lane] = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-    reinterpret_cast<double2*>(lntab)[lane] = reinterpret_cast<const double2*>(g_ln_table)[lane];
-    reinterpret_cast<double2*>(lntab)[lane + 64] = reinterpret_cast<const double2*>(g_ln_table)[lane + 64];
-    __syncthreads();                               // (one wave per workgroup: no wait)
+    philox_stage_tables(lane, sctab, lntab);
     const long long c = tile / p.tiles_per_ctrl;
     const long long kb = (tile - c * p.tiles_per_ctrl) * 64;
     const int nk = (int)((p.K - kb < 64) ? (p.K - kb) : 64);
@@ -82,27 +77,11 @@ __global__ __launch_bounds__(64, grad_philox_min_waves(N)) void mc_fid_grad_phil
     }
     const bool live = lane < nk;
     const double sigma = p.sigma_rows ? p.sigma_rows[c] : p.sigma;
-    // this lane's G elements start at E; the pairs (2 ctr, 2 ctr + 1) that cover them start at ctr = E >> 1
+    // this lane's G elements start at stream element E
     const unsigned long long E =
         p.offset + (unsigned long long)((p.shared ? 0ll : c * p.K) + kb + lane) * (unsigned long long)G;
     double gl[G];
-    if (live) {
-        // (as in mc_fid_chain_philox_kernel: every gl[i] is a select between two VALUES of neighbouring pairs)
-        const unsigned long long c0 = E >> 1;
-        const bool odd = (E & 1ull) != 0ull;
-        double sn_prev = 0.0;
-#pragma unroll
-        for (int t = 0; t < NPAIR; ++t) {
-            double amp, cs, sn;
-            philox_pair(p.seed, c0 + (unsigned long long)t, sigma, lntab, sctab, amp, cs, sn);
-            // rounded products, as philox_normal_kernel stores them (opaque: never contracted into a consumer)
-            double a = amp * cs, b = amp * sn;
-            asm volatile("" : "+v"(a), "+v"(b));
-            if (2 * t < G) gl[2 * t] = odd ? b : a;
-            if (t >= 1 && 2 * t - 1 < G) gl[2 * t - 1] = odd ? a : sn_prev;
-            sn_prev = b;
-        }
-    }
+    if (live) philox_lane_draws<G>(p.seed, E, sigma, lntab, sctab, gl);
 
     constexpr int R = rc::grad_batch_rows(N);      // rows of the eigenvector matrix per QL pass (grad_core.h)
     constexpr int NP = rc::grad_passes(N);

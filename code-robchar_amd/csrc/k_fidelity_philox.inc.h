@@ -4,10 +4,10 @@
 // draw tensor exists: lane (c, k) regenerates its 3N normals from the stream of rc_draws_philox_f64,
 //     element  offset + ((c K + k) N + i) 3 + s   of stream `seed`, scaled by sigma (per controller row: all sigma levels of an
 //     algorithm go through one launch with the controller rows tiled L times),
-// with the SAME routine philox_normal_kernel uses (philox_pair): the fidelities are bit-identical to the two-kernel route
-// (tests/test_gpu_rng.py), and oracle/philox_host.py still regenerates any element on the host.
-// Cost (DESIGN.md 8 xiii): 3N/2 + 1 Box-Muller pairs per sample (the pair grid straddles samples: one output of the first or the
-// last pair belongs to a neighbour), ~150 VALU instructions each - about what the fidelity itself costs at N = 7; what it saves
+// with philox_lane_draws (philox_core.inc.h: the bits philox_normal_kernel stores): the fidelities are bit-identical to the
+// two-kernel route (tests/test_gpu_rng.py), and oracle/philox_host.py still regenerates any element on the host.
+// Cost (DESIGN.md 8 xiii): 3N/2 + 1 Box-Muller pairs per sample, ~150 VALU instructions each - about what the fidelity itself
+// costs at N = 7; what it saves
 // is the generator's 16-byte store per pair, the fidelity kernel's read of it, and the 24 N bytes per sample of HBM capacity
 // (BASELINE config 4: 16.8 GB per sigma level).
 //
@@ -29,7 +29,6 @@ constexpr int fid_philox_min_waves(int n, int mode) {
 template <int N, int MODE>
 __global__ __launch_bounds__(64, fid_philox_min_waves(N, MODE)) void mc_fid_chain_philox_kernel(const FidParams p, const PhiloxDraws q) {
     constexpr int G = 3 * N;                       // doubles per sample
-    constexpr int NP = G / 2 + 1;                  // Box-Muller pairs that cover G consecutive elements from either parity
     constexpr int CH = 4;                          // lanes per pass of the last-resort routine (work vectors in LDS)
     __shared__ __attribute__((aligned(16))) double sctab[128];
     __shared__ __attribute__((aligned(16))) double lntab[256];
@@ -37,10 +36,7 @@ __global__ __launch_bounds__(64, fid_philox_min_waves(N, MODE)) void mc_fid_chai
 
     const int lane = threadIdx.x;
     const long long tile = blockIdx.x;             // wave-uniform
-    reinterpret_cast<double2*>(sctab)[lane] = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-    reinterpret_cast<double2*>(lntab)[lane] = reinterpret_cast<const double2*>(g_ln_table)[lane];
-    reinterpret_cast<double2*>(lntab)[lane + 64] = reinterpret_cast<const double2*>(g_ln_table)[lane + 64];
-    __syncthreads();                               // (one wave per workgroup: no wait)
+    philox_stage_tables(lane, sctab, lntab);
     const long long c = tile / p.tiles_per_ctrl;
     const long long kb = (tile - c * p.tiles_per_ctrl) * 64;
     const int nk = (int)((p.K - kb < 64) ? (p.K - kb) : 64);
@@ -59,29 +55,10 @@ __global__ __launch_bounds__(64, fid_philox_min_waves(N, MODE)) void mc_fid_chai
         return;
     }
     const double sigma = q.sigma_rows ? q.sigma_rows[c] : q.sigma;
-    // this lane's G elements start at E; the pairs (2 ctr, 2 ctr + 1) that cover them start at ctr = E >> 1
+    // this lane's G elements start at stream element E
     const unsigned long long E = q.offset + (unsigned long long)(c * p.K + kb + lane) * (unsigned long long)G;
     double gl[G];
-    if (lane < nk) {
-        // pair t = counter (E >> 1) + t holds the elements (2 t, 2 t + 1) after E when E is even and (2 t - 1, 2 t) when it is
-        // odd: every gl[i] is a select between two VALUES of neighbouring pairs (written this way - not as v[i + odd] on an
-        // array of pair values - because a select between array elements becomes a load from a selected address: scratch)
-        const unsigned long long c0 = E >> 1;
-        const bool odd = (E & 1ull) != 0ull;
-        double sn_prev = 0.0;
-#pragma unroll
-        for (int t = 0; t < NP; ++t) {
-            double amp, cs, sn;
-            philox_pair(q.seed, c0 + (unsigned long long)t, sigma, lntab, sctab, amp, cs, sn);
-            // (rounded products, as philox_normal_kernel stores them: left to the compiler they would be contracted into the
-            // fma that forms the matrix entry - a different rounding than the two-kernel route's)
-            double a = amp * cs, b = amp * sn;
-            asm volatile("" : "+v"(a), "+v"(b));      // (opaque: __dmul_rn is a plain multiply to the optimiser)
-            if (2 * t < G) gl[2 * t] = odd ? b : a;
-            if (t >= 1 && 2 * t - 1 < G) gl[2 * t - 1] = odd ? a : sn_prev;
-            sn_prev = b;
-        }
-    }
+    if (lane < nk) philox_lane_draws<G>(q.seed, E, sigma, lntab, sctab, gl);
 
     double f = 0.0;
     bool ok = true;

@@ -3,7 +3,8 @@
 //
 // Included by robchar_grad.hip inside its anonymous namespace after k_fidelity_grad.inc.h; not a stand-alone header.
 // Tiling, LDS-DMA staging, NaN-row rule and the fast / textbook QL routes are mc_fid_grad_kernel's (the staging block is
-// repeated here rather than shared, so that the gradient kernel's code stays untouched).  Per lane: sens_core.h.  The
+// written out here: through stage_tile_draws<G, PH, 0> the listing stays within every resource bound, but the kernel with all
+// outputs measured 1.1 - 1.4 % slower at N = 5, 9 - profiles/shared_leaves_listing.txt).  Per lane: sens_core.h.  The
 // sample's draws are needed again after the QL - for the unit phases re/r, im/r of the couplings and for the radial
 // derivative rho = sum g dF/dg - and are re-read from global memory then (every lane its own 24 N contiguous bytes, hot in
 // L2 from the staging) instead of being held in 6 N registers across the QL.

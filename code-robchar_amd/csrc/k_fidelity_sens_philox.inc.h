@@ -3,8 +3,7 @@
 // (c, k) makes its 3 N normals from the stream of rc_draws_philox_f64,
 //     element  offset + ((c K + k) N + i) 3 + s   of stream `seed`, scaled by sigma or by sigma_rows[c] (wave-uniform: all sigma
 //     levels of an algorithm go through one launch with the controller rows tiled L times),
-// with the routine philox_normal_kernel uses (philox_pair, philox_core.inc.h); the rounded products amp * cos, amp * sin are kept
-// opaque so that none is contracted into the sum that forms a matrix entry.  Tiling, NaN-row rule, per-sample arithmetic
+// with philox_lane_draws (philox_core.inc.h: the bits philox_normal_kernel stores).  Tiling, NaN-row rule, per-sample arithmetic
 // (sens_core.h / grad_core.h), the order of the wave sums and the second pass of the row means (mc_fid_grad_mean_kernel) are
 // mc_fid_sens_kernel's: fid, sens and mean are bit-identical to philox_normal_kernel followed by mc_fid_sens_kernel.
 //
@@ -32,14 +31,13 @@
 // (single-pass sizes above 9 hold their draws in LDS too; with 6 here, N = 7 fits two waves per SIMD, 256 registers - the A/B
 // against the registers: DESIGN.md, the sensitivity kernels)
 constexpr bool sens_philox_hold_in_registers(int n) { return rc::sens_passes(n) == 1 && n <= 9; }
-// from the listing: 60 / 108 registers at N = 2, 3 (four waves), 152 / 196 / 252 at N = 4 .. 6 (two), from N = 7
+// from the listing: 58 / 108 registers at N = 2, 3 (four waves), 152 / 196 / 252 at N = 4 .. 6 (two), from N = 7
 // (294: the 42 held values beside mc_fid_sens_kernel's 256) one wave
 constexpr int sens_philox_min_waves(int n) { return n <= 3 ? 4 : ((n <= 6 || (n == 7 && !sens_philox_hold_in_registers(7))) ? 2 : 1); }
 
 template <int N>
 __global__ __launch_bounds__(64, sens_philox_min_waves(N)) void mc_fid_sens_philox_kernel(const SensPhiloxParams p) {
     constexpr int G = 3 * N;                       // doubles per sample
-    constexpr int NPAIR = G / 2 + 1;               // Box-Muller pairs that cover G consecutive elements from either parity
     constexpr int kWork = 2 * N + N * N;           // doubles per sample of the textbook routine
     constexpr int CH = N <= 8 ? 8 : 4;             // lanes of it at a time
     constexpr bool HOLD = sens_philox_hold_in_registers(N);
@@ -50,10 +48,7 @@ __global__ __launch_bounds__(64, sens_philox_min_waves(N)) void mc_fid_sens_phil
 
     const int lane = threadIdx.x;
     const long long tile = blockIdx.x;             // wave-uniform
-    reinterpret_cast<double2*>(sctab)[lane] = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-    reinterpret_cast<double2*>(lntab)[lane] = reinterpret_cast<const double2*>(g_ln_table)[lane];
-    reinterpret_cast<double2*>(lntab)[lane + 64] = reinterpret_cast<const double2*>(g_ln_table)[lane + 64];
-    __syncthreads();                               // (one wave per workgroup: no wait)
+    philox_stage_tables(lane, sctab, lntab);
     const long long c = tile / p.tiles_per_ctrl;
     const long long kb = (tile - c * p.tiles_per_ctrl) * 64;
     const int nk = (int)((p.K - kb < 64) ? (p.K - kb) : 64);
@@ -80,26 +75,10 @@ __global__ __launch_bounds__(64, sens_philox_min_waves(N)) void mc_fid_sens_phil
     }
     const bool live = lane < nk;
     const double sigma = p.sigma_rows ? p.sigma_rows[c] : p.sigma;
-    // this lane's G elements start at E; the pairs (2 ctr, 2 ctr + 1) that cover them start at ctr = E >> 1
+    // this lane's G elements start at stream element E
     const unsigned long long E = p.offset + (unsigned long long)(c * p.K + kb + lane) * (unsigned long long)G;
     double gl[G];
-    if (live) {
-        // (as in mc_fid_chain_philox_kernel: every gl[i] is a select between two VALUES of neighbouring pairs)
-        const unsigned long long c0 = E >> 1;
-        const bool odd = (E & 1ull) != 0ull;
-        double sn_prev = 0.0;
-#pragma unroll
-        for (int t = 0; t < NPAIR; ++t) {
-            double amp, cs, sn;
-            philox_pair(p.seed, c0 + (unsigned long long)t, sigma, lntab, sctab, amp, cs, sn);
-            // rounded products, as philox_normal_kernel stores them (opaque: never contracted into a consumer)
-            double a = amp * cs, b = amp * sn;
-            asm volatile("" : "+v"(a), "+v"(b));
-            if (2 * t < G) gl[2 * t] = odd ? b : a;
-            if (t >= 1 && 2 * t - 1 < G) gl[2 * t - 1] = odd ? a : sn_prev;
-            sn_prev = b;
-        }
-    }
+    if (live) philox_lane_draws<G>(p.seed, E, sigma, lntab, sctab, gl);
 
     constexpr int R = rc::sens_batch_rows(N);      // rows of the eigenvector matrix per QL pass (sens_core.h)
     constexpr int NP = rc::sens_passes(N);

@@ -5,9 +5,8 @@
 // Included by robchar_times.hip inside its anonymous namespace (after philox_core.inc.h); not a stand-alone header.
 // Same tiling as mc_fid_chain_kernel (k_fidelity_chain.inc.h): one wave per 64-sample tile of ONE controller, the controller row
 // wave-uniform.  The tensor kernel brings the tile's draws in by LDS-DMA in phases with the streaming load policy and reads them
-// back transposed; the other one regenerates them with philox_pair exactly as mc_fid_chain_philox_kernel does (stream element
-// offset + ((c K + k) N + i) 3 + s, rounded products kept opaque), so its outputs are bit-identical to philox_normal followed by
-// the tensor kernel.
+// back transposed (stage_tile_draws); the other one regenerates them with philox_lane_draws (philox_core.inc.h; stream element
+// offset + ((c K + k) N + i) 3 + s), so its outputs are bit-identical to philox_normal followed by the tensor kernel.
 //
 // Outputs (each optional): fid[M][C][K] - M slabs, each an ordinary [C][K] fidelity tensor: a wave stores 64 consecutive doubles
 // per time -, wsum[C][K] and fmin[C][K] (TimesAcc).  A NaN controller row gives NaN in every output; its draws are not read.
@@ -53,7 +52,6 @@ __global__ __launch_bounds__(64, times_min_waves(N)) void mc_fid_times_kernel(co
     constexpr int G = 3 * N;                       // doubles per sample
     constexpr int PH = times_phases(N);
     constexpr int SP = 64 / PH;                    // samples per staging phase
-    constexpr int kPhaseBytes = SP * G * 8;
     constexpr int CH = (SP * G) / (4 * N);         // samples of the textbook routine that fit the staging buffer at a time
     static_assert(CH >= 1, "staging buffer too small for the textbook routine");
     __shared__ __attribute__((aligned(16))) double stage[SP * G];
@@ -84,40 +82,7 @@ __global__ __launch_bounds__(64, times_min_waves(N)) void mc_fid_times_kernel(co
     // HBM -> LDS -> registers (see mc_fid_chain_kernel): the tile's draws are one contiguous run of nk * G doubles
     const char* src = (const char*)(p.draws + c * p.draw_cstride + kb * G);
     double gl[G];
-#pragma unroll
-    for (int ph = 0; ph < PH; ++ph) {
-        const int first = ph * SP;
-        if (first < nk) {                          // wave-uniform
-            const int cnt = (nk - first < SP) ? (nk - first) : SP;
-            const int bytes = cnt * G * 8;
-            const char* ps = src + (long long)first * G * 8;
-            if (p.align16 && !(cnt & 1)) {
-#pragma unroll
-                for (int it = 0; it < (kPhaseBytes + 1023) / 1024; ++it) {
-                    const int off = it * 1024 + lane * 16;
-                    if (off < bytes)
-                        __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off), (rc_lptr_t)((char*)stage + it * 1024), 16, 0,
-                                                         rckp::kDrawLoadAux);
-                }
-            } else {
-#pragma unroll 2
-                for (int it = 0; it < (kPhaseBytes + 255) / 256; ++it) {
-                    const int off = it * 256 + lane * 4;
-                    if (off < bytes)
-                        __builtin_amdgcn_global_load_lds((rc_gptr_t)(ps + off), (rc_lptr_t)((char*)stage + it * 256), 4, 0,
-                                                         rckp::kDrawLoadAux);
-                }
-            }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // DMA landed
-            int rel = lane - first;
-            asm volatile("" : "+v"(rel));                             // one base address + immediate offsets
-            if (rel >= 0 && rel < cnt) {
-#pragma unroll
-                for (int i = 0; i < G; ++i) gl[i] = stage[rel * G + i];
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");       // reads done before the buffer is refilled
-        }
-    }
+    stage_tile_draws<G, PH>(src, nk, lane, p.align16, stage, gl);
     __builtin_amdgcn_s_setprio(0);
     __syncthreads();                               // the table copy has landed (one wave per workgroup: no wait)
 
@@ -158,7 +123,6 @@ __global__ __launch_bounds__(64, times_min_waves(N)) void mc_fid_times_kernel(co
 template <int N>
 __global__ __launch_bounds__(64, times_philox_min_waves(N)) void mc_fid_times_philox_kernel(const TimesParams p) {
     constexpr int G = 3 * N;                       // doubles per sample
-    constexpr int NP = G / 2 + 1;                  // Box-Muller pairs that cover G consecutive elements from either parity
     constexpr int CH = 4;                          // lanes per pass of the textbook routine (draws and work vectors in LDS)
     __shared__ __attribute__((aligned(16))) double sctab[128];
     __shared__ __attribute__((aligned(16))) double lntab[256];
@@ -166,10 +130,7 @@ __global__ __launch_bounds__(64, times_philox_min_waves(N)) void mc_fid_times_ph
 
     const int lane = threadIdx.x;
     const long long tile = blockIdx.x;             // wave-uniform
-    reinterpret_cast<double2*>(sctab)[lane] = reinterpret_cast<const double2*>(g_sincos_table)[lane];
-    reinterpret_cast<double2*>(lntab)[lane] = reinterpret_cast<const double2*>(g_ln_table)[lane];
-    reinterpret_cast<double2*>(lntab)[lane + 64] = reinterpret_cast<const double2*>(g_ln_table)[lane + 64];
-    __syncthreads();                               // (one wave per workgroup: no wait)
+    philox_stage_tables(lane, sctab, lntab);
     const long long c = tile / p.tiles_per_ctrl;
     const long long kb = (tile - c * p.tiles_per_ctrl) * 64;
     const int nk = (int)((p.K - kb < 64) ? (p.K - kb) : 64);
@@ -188,26 +149,10 @@ __global__ __launch_bounds__(64, times_philox_min_waves(N)) void mc_fid_times_ph
         return;
     }
     const double sigma = p.sigma_rows ? p.sigma_rows[c] : p.sigma;
-    // this lane's G elements start at E; the pairs (2 ctr, 2 ctr + 1) that cover them start at ctr = E >> 1
+    // this lane's G elements start at stream element E
     const unsigned long long E = p.offset + (unsigned long long)(at + lane) * (unsigned long long)G;
     double gl[G];
-    if (lane < nk) {
-        // (every gl[i] a select between two VALUES of neighbouring pairs: see mc_fid_chain_philox_kernel)
-        const unsigned long long c0 = E >> 1;
-        const bool odd = (E & 1ull) != 0ull;
-        double sn_prev = 0.0;
-#pragma unroll
-        for (int t = 0; t < NP; ++t) {
-            double amp, cs, sn;
-            philox_pair(p.seed, c0 + (unsigned long long)t, sigma, lntab, sctab, amp, cs, sn);
-            // (rounded products, as philox_normal_kernel stores them)
-            double a = amp * cs, b = amp * sn;
-            asm volatile("" : "+v"(a), "+v"(b));
-            if (2 * t < G) gl[2 * t] = odd ? b : a;
-            if (t >= 1 && 2 * t - 1 < G) gl[2 * t - 1] = odd ? a : sn_prev;
-            sn_prev = b;
-        }
-    }
+    if (lane < nk) philox_lane_draws<G>(p.seed, E, sigma, lntab, sctab, gl);
 
     const TimesDst dst{p.fid ? p.fid + at + lane : nullptr, p.C * p.K};
     rc::TimesAcc acc{0.0, 0.0};

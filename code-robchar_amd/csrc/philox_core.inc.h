@@ -161,6 +161,42 @@ __device__ __forceinline__ double philox_element(unsigned long long seed, unsign
     double amp, cs, sn;
     philox_pair(seed, e >> 1, scale, lntab, sctab, amp, cs, sn);
     double v = (e & 1ull) ? amp * sn : amp * cs;
-    asm volatile("" : "+v"(v));                    // rounded product, never contracted into its consumer (see the kernel)
+    asm volatile("" : "+v"(v));                    // rounded product, never contracted into its consumer (philox_lane_draws)
     return v;
+}
+
+// The per-wave LDS copies of the two tables (sctab[128], lntab[256], both 16-byte aligned): lane l copies entry l of the first and
+// entries l, l + 64 of the second as double2.  The barrier costs nothing with one wave per workgroup.
+__device__ __forceinline__ void philox_stage_tables(int lane, double* sctab, double* lntab) {
+    reinterpret_cast<double2*>(sctab)[lane] = reinterpret_cast<const double2*>(g_sincos_table)[lane];
+    reinterpret_cast<double2*>(lntab)[lane] = reinterpret_cast<const double2*>(g_ln_table)[lane];
+    reinterpret_cast<double2*>(lntab)[lane + 64] = reinterpret_cast<const double2*>(g_ln_table)[lane + 64];
+    __syncthreads();
+}
+
+// This lane's G consecutive elements of stream `seed` from element E on, into gl: what philox_normal_kernel would have stored
+// there, bit for bit.  G / 2 + 1 Box-Muller pairs cover G elements from either parity of E (the pair grid straddles samples: one
+// output of the first or of the last pair belongs to a neighbour).  Pair t = counter (E >> 1) + t holds the elements
+// (2 t, 2 t + 1) after E when E is even and (2 t - 1, 2 t) when it is odd, so every gl[i] is a select between two VALUES of
+// neighbouring pairs.  It is written that way, and not as v[i + odd] on an array of pair values, because a select between array
+// elements becomes a load from a selected address: the array would go to scratch.
+// The products amp * cs, amp * sn are rounded as philox_normal_kernel stores them and made opaque (__dmul_rn is a plain multiply
+// to the optimiser): left to the compiler they would be contracted into the fma that forms the consumer's matrix entry - another
+// rounding than the two-kernel route's, and the generated-draws kernels would no longer be bit-identical to it.
+template <int G>
+__device__ __forceinline__ void philox_lane_draws(unsigned long long seed, unsigned long long E, double scale, const double* lntab,
+                                                  const double* sctab, double (&gl)[G]) {
+    const unsigned long long c0 = E >> 1;
+    const bool odd = (E & 1ull) != 0ull;
+    double sn_prev = 0.0;
+#pragma unroll
+    for (int t = 0; t < G / 2 + 1; ++t) {
+        double amp, cs, sn;
+        philox_pair(seed, c0 + (unsigned long long)t, scale, lntab, sctab, amp, cs, sn);
+        double a = amp * cs, b = amp * sn;
+        asm volatile("" : "+v"(a), "+v"(b));
+        if (2 * t < G) gl[2 * t] = odd ? b : a;
+        if (t >= 1 && 2 * t - 1 < G) gl[2 * t - 1] = odd ? a : sn_prev;
+        sn_prev = b;
+    }
 }

@@ -20,8 +20,7 @@ using rckp::GradPhiloxParams;
 using rckp::GradListedParams;
 using rckp::SensParams;
 using rckp::SensPhiloxParams;
-typedef __attribute__((address_space(1))) const void* rc_gptr_t;
-typedef __attribute__((address_space(3))) void* rc_lptr_t;
+#include "tile_stage.inc.h"
 
 // tiles in which some sample's QL hit the sweep cap and took the textbook routine (diagnostic; rare path only); counted by
 // mc_fid_grad_kernel, mc_fid_grad_philox_kernel and mc_fid_grad_listed_kernel

@@ -39,6 +39,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <atomic>
+#include <initializer_list>
 #include <mutex>
 #include <unordered_map>
 #include <thread>
@@ -104,8 +105,7 @@ using rckp::StaticH;
 using rckp::FidParams;
 using rckp::RingRepairList;
 
-typedef __attribute__((address_space(1))) const void* rc_gptr_t;
-typedef __attribute__((address_space(3))) void* rc_lptr_t;
+#include "tile_stage.inc.h"
 
 #include "k_fidelity_chain.inc.h"
 #include "k_fidelity_dense.inc.h"
@@ -358,6 +358,15 @@ int enqueue_expm(hipStream_t s, int N, int in, int out, const double* h0_diag, c
     return RC_OK;
 }
 
+// FidParams::align16 and its like: the draws base and every controller's run of K * 3N doubles are 16-byte aligned
+int draws_align16(const double* draws, long long draw_cstride) {
+    return (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
+}
+// bytes of a draw tensor whose controllers are `stride` doubles apart (0: one set shared by all)
+size_t draws_bytes(long long C, long long K, int N, long long stride) {
+    return (stride == 0 ? (size_t)K * N * 3 : ((size_t)(C - 1) * stride + (size_t)K * N * 3)) * sizeof(double);
+}
+
 int enqueue_fidelity(hipStream_t s, int kernel, int N, int in, int out, const double* h0_diag,
                      const double* h0_offdiag, int ring, const double* ctrl, const double* draws,
                      long long draw_cstride, long long C, long long K, double* fid) {
@@ -387,7 +396,7 @@ int enqueue_fidelity(hipStream_t s, int kernel, int N, int in, int out, const do
         p.ntiles = C * p.tiles_per_ctrl;
         p.in = in;
         p.out = out;
-        p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
+        p.align16 = draws_align16(draws, draw_cstride);
         fill_h0(p.h0, N, h0_diag, h0_offdiag);
         if (p.ntiles > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
         const dim3 grid((unsigned)p.ntiles);
@@ -465,7 +474,7 @@ int enqueue_fidelity(hipStream_t s, int kernel, int N, int in, int out, const do
         p.ntiles = C * p.tiles_per_ctrl;
         p.in = in;
         p.out = out;
-        p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
+        p.align16 = draws_align16(draws, draw_cstride);
         p.stamps = g_stamps;
         fill_h0(p.h0, N, h0_diag, h0_offdiag);
         // chains of 17 .. 24 spins (round 5): the register-resident general-adjugate instantiation (one wave per SIMD) for the
@@ -1353,44 +1362,62 @@ void run_gather_share_locked(GatherJob* j) {
 // ------------------------------------------------------------------------------------------------
 // C ABI
 // ------------------------------------------------------------------------------------------------
-// sum of the `slots` unsigned 64-bit counters behind a device symbol (synchronises the device); optionally zeroes them
-template <typename Sym>
-static long long read_tile_counter(int device, int reset, const Sym& symbol, int slots) {
+// Sum of a diagnostic tile counter (synchronises the device; optionally zeroes it): `slots` unsigned 64-bit counters at each of
+// the n device addresses addr_of[u]() gives (a hipError_t).  `what`: the text of any failure; NULL: a counter of the chain /
+// ring kernels - this unit's copy, then the second unit's (robchar_large.hip: chains of 17 .. 24 spins, rings of 11 .. 16) -,
+// whose texts say what failed and in which unit.
+typedef int (*CounterAddr)(void**);
+static long long read_tile_counter(int device, int reset, const CounterAddr* addr_of, int n, int slots, const char* what) {
     if (hipSetDevice(device) != hipSuccess) {
         (void)hipGetLastError();
         return fail(RC_EHIP, "hipSetDevice failed");
     }
-    unsigned long long v[64] = {0};
-    void* addr = nullptr;
-    if (hipDeviceSynchronize() != hipSuccess || hipGetSymbolAddress(&addr, HIP_SYMBOL(symbol)) != hipSuccess ||
-        hipMemcpy(v, addr, sizeof(unsigned long long) * slots, hipMemcpyDeviceToHost) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(RC_EHIP, "reading the tile counter failed");
-    }
-    if (reset && hipMemset(addr, 0, sizeof(unsigned long long) * slots) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(RC_EHIP, "resetting the tile counter failed");
-    }
+    const size_t nb = sizeof(unsigned long long) * slots;
     unsigned long long sum = 0;
-    for (int i = 0; i < slots; ++i) sum += v[i];
-    // the same counter of the second translation unit (robchar_large.hip: chains of 17 .. 24 spins, rings of 11 .. 16)
-    void* addr2 = nullptr;
-    if (rc_large_counter_addr(slots == 1 ? 0 : 1, &addr2) != hipSuccess || !addr2 ||
-        hipMemcpy(v, addr2, sizeof(unsigned long long) * slots, hipMemcpyDeviceToHost) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(RC_EHIP, "reading the tile counter (second unit) failed");
+    for (int u = 0; u < n; ++u) {
+        const std::string unit = u ? " the tile counter (second unit) failed" : " the tile counter failed";
+        unsigned long long v[64] = {0};
+        void* addr = nullptr;
+        if ((u == 0 && hipDeviceSynchronize() != hipSuccess) || addr_of[u](&addr) != hipSuccess || !addr ||
+            hipMemcpy(v, addr, nb, hipMemcpyDeviceToHost) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RC_EHIP, what ? what : "reading" + unit);
+        }
+        if (reset && hipMemset(addr, 0, nb) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(RC_EHIP, what ? what : "resetting" + unit);
+        }
+        for (int i = 0; i < slots; ++i) sum += v[i];
     }
-    if (reset && hipMemset(addr2, 0, sizeof(unsigned long long) * slots) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(RC_EHIP, "resetting the tile counter (second unit) failed");
-    }
-    for (int i = 0; i < slots; ++i) sum += v[i];
     return (long long)sum;
 }
 
 // ------------------------------------------------------------------------------------------------
 // the derivative family (robchar_grad.hip): what its entries share on the host
 // ------------------------------------------------------------------------------------------------
+// Where a sample's draws come from, checked the same way by the derivative and the readout-time entries, in two steps (the
+// derivative entries refuse a call without outputs between them).  `stride` set: the entry takes a draw tensor; NULL: it
+// generates its draws from `sigma` / `sigma_rows`.
+// First the stride: the default is filled in, an overlapping one refused.
+static int check_draw_stride(int N, long long* stride, long long K) {
+    if (stride && *stride < 0) *stride = K * N * 3;
+    if (stride && *stride != 0 && *stride < K * N * 3) return fail(RC_EINVAL, "draws_ctrl_stride overlaps controllers");
+    return RC_OK;
+}
+// Then: a usable sigma where the draws are generated, the empty case (*empty, RC_OK), the NULL pointers and the tile limit.
+static int check_draw_source(const void* ctrl, const void* draws, const long long* stride, double sigma, const void* sigma_rows,
+                             long long C, long long K, bool* empty) {
+    if (!stride && !sigma_rows && !(sigma >= 0.0 && sigma < HUGE_VAL))
+        return fail(RC_EINVAL, "sigma must be finite and non-negative (or give sigma_rows)");
+    if (C == 0 || K == 0) {
+        *empty = true;
+        return RC_OK;
+    }
+    if (!ctrl || (stride && !draws)) return fail(RC_EINVAL, "NULL array pointer");
+    if ((C * ((K + 63) / 64)) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    return RC_OK;
+}
+
 // Argument checks of the entries of the derivative family - all before any HIP call.  `what`: the kernel's name in the
 // N > RC_MAX_NSPIN_GRAD refusal; `outs`: the output arguments, of which `any_out` says whether one is set.  `stride` set: the
 // entry takes a draw tensor (its default is filled in); NULL: it generates its draws from `sigma` / `sigma_rows`.
@@ -1403,18 +1430,9 @@ static int check_deriv_args(const char* what, const char* outs, int N, int in, i
     if (N > RC_MAX_NSPIN_GRAD)
         return fail(RC_ENOSUP, std::string("the ") + what + (stride ? " kernel" : " kernel with draws generated inside it") +
                                    " supports chains of N <= " + std::to_string(RC_MAX_NSPIN_GRAD) + " spins");
-    if (stride && *stride < 0) *stride = K * N * 3;
-    if (stride && *stride != 0 && *stride < K * N * 3) return fail(RC_EINVAL, "draws_ctrl_stride overlaps controllers");
+    if (int rc = check_draw_stride(N, stride, K)) return rc;
     if (!any_out) return fail(RC_EINVAL, std::string("no output requested (") + outs + " are all NULL)");
-    if (!stride && !sigma_rows && !(sigma >= 0.0 && sigma < HUGE_VAL))
-        return fail(RC_EINVAL, "sigma must be finite and non-negative (or give sigma_rows)");
-    if (C == 0 || K == 0) {
-        *empty = true;
-        return RC_OK;
-    }
-    if (!ctrl || (stride && !draws)) return fail(RC_EINVAL, "NULL array pointer");
-    if ((C * ((K + 63) / 64)) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
-    return RC_OK;
+    return check_draw_source(ctrl, draws, stride, sigma, sigma_rows, C, K, empty);
 }
 static const char kGradOuts[] = "fid_out, grad_out and mean_out", kSensOuts[] = "fid_out, sens_out and mean_out";
 
@@ -1455,7 +1473,7 @@ static int enqueue_grad(hipStream_t s, int N, int in, int out, const double* h0_
     fill_deriv_params(p, N, in, out, h0_diag, h0_offdiag, ctrl, C, K, fid);
     p.draws = draws;
     p.draw_cstride = draw_cstride;
-    p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
+    p.align16 = draws_align16(draws, draw_cstride);
     p.grad = grad;
     return launch_with_part(s, p, mean != nullptr, N + 2, "rc_grad_launch", [&] { return rc_grad_launch(N, (void*)s, &p, mean); });
 }
@@ -1466,7 +1484,7 @@ static int enqueue_sens(hipStream_t s, int N, int in, int out, const double* h0_
     fill_deriv_params(p, N, in, out, h0_diag, h0_offdiag, ctrl, C, K, fid);
     p.draws = draws;
     p.draw_cstride = draw_cstride;
-    p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
+    p.align16 = draws_align16(draws, draw_cstride);
     p.sens = sens;
     return launch_with_part(s, p, mean != nullptr, 3 * N + 2, "rc_sens_launch",
                             [&] { return rc_sens_launch(N, (void*)s, &p, mean); });
@@ -1482,9 +1500,7 @@ static int blocking_deriv(decltype(&enqueue_grad) enqueue, int per_sample, int p
     std::lock_guard<std::mutex> lk(g_ctx[device].mu);
     Staging ws;
     if (int rc = get_ctx(device, &ws.ctx)) return rc;
-    const size_t nb_draw = (draws_ctrl_stride == 0 ? (size_t)K * N * 3 : ((size_t)(C - 1) * draws_ctrl_stride + (size_t)K * N * 3)) *
-                           sizeof(double);
-    const size_t nb_fid = (size_t)C * K * sizeof(double);
+    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_draw = draws_bytes(C, K, N, draws_ctrl_stride);
     const int s_ctrl = ws.in(controllers, (size_t)C * (N + 1) * sizeof(double)), s_draw = ws.in(draws, nb_draw),
               s_fid = ws.out(fid_out, nb_fid), s_second = ws.out(second_out, nb_fid * per_sample),
               s_mean = ws.out(mean_out, (size_t)C * per_row * sizeof(double));
@@ -1550,8 +1566,16 @@ int rc_device_count(void) {
 
 const char* rc_last_error(void) { return g_last_error.c_str(); }
 
-long long rc_stats_general_tiles(int device, int reset) { return read_tile_counter(device, reset, g_general_tiles, 1); }
-long long rc_stats_polish_tiles(int device, int reset) { return read_tile_counter(device, reset, g_polish_tiles, 64); }
+long long rc_stats_general_tiles(int device, int reset) {
+    const CounterAddr units[2] = {[](void** a) { return (int)hipGetSymbolAddress(a, HIP_SYMBOL(g_general_tiles)); },
+                                  [](void** a) { return rc_large_counter_addr(0, a); }};
+    return read_tile_counter(device, reset, units, 2, 1, nullptr);
+}
+long long rc_stats_polish_tiles(int device, int reset) {
+    const CounterAddr units[2] = {[](void** a) { return (int)hipGetSymbolAddress(a, HIP_SYMBOL(g_polish_tiles)); },
+                                  [](void** a) { return rc_large_counter_addr(1, a); }};
+    return read_tile_counter(device, reset, units, 2, 64, nullptr);
+}
 
 int rc_set_fidelity_kernel(int kernel) {
     if (kernel < RC_KERNEL_AUTO || kernel > RC_KERNEL_RING_HH) return fail(RC_EINVAL, "unknown kernel id");
@@ -1623,25 +1647,13 @@ int rc_mc_fidelity_grad_f64(int device, int N, int in, int out, const double* h0
                           K, fid_out, grad_out, mean_out);
 }
 
-// one unsigned 64-bit counter of the third unit, behind rc_grad_counter_addr / rc_sens_counter_addr (synchronises the device)
-static long long read_tile_counter(int device, int reset, int (*addr_of)(void**), const char* what) {
-    if (hipSetDevice(device) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(RC_EHIP, "hipSetDevice failed");
-    }
-    unsigned long long v = 0;
-    void* addr = nullptr;
-    if (hipDeviceSynchronize() != hipSuccess || addr_of(&addr) != hipSuccess || !addr ||
-        hipMemcpy(&v, addr, sizeof v, hipMemcpyDeviceToHost) != hipSuccess ||
-        (reset && hipMemset(addr, 0, sizeof v) != hipSuccess)) {
-        (void)hipGetLastError();
-        return fail(RC_EHIP, what);
-    }
-    return (long long)v;
+// (one unsigned 64-bit counter of the third or fourth unit; a failed reset reports as a failed read)
+static long long read_unit_counter(int device, int reset, CounterAddr addr_of, const char* what) {
+    return read_tile_counter(device, reset, &addr_of, 1, 1, what);
 }
 
 long long rc_stats_grad_general_tiles(int device, int reset) {
-    return read_tile_counter(device, reset, rc_grad_counter_addr, "reading the gradient kernel's tile counter failed");
+    return read_unit_counter(device, reset, rc_grad_counter_addr, "reading the gradient kernel's tile counter failed");
 }
 
 int rc_mc_fidelity_sens_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag, const double* h0_offdiag,
@@ -1670,7 +1682,7 @@ int rc_mc_fidelity_sens_f64(int device, int N, int in, int out, const double* h0
 }
 
 long long rc_stats_sens_general_tiles(int device, int reset) {
-    return read_tile_counter(device, reset, rc_sens_counter_addr, "reading the sensitivity kernel's tile counter failed");
+    return read_unit_counter(device, reset, rc_sens_counter_addr, "reading the sensitivity kernel's tile counter failed");
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1689,17 +1701,8 @@ static int check_times_args(int N, int in, int out, int ring, const void* ctrl, 
     if (M < 1 || M > RC_MAX_TIMES) return fail(RC_EINVAL, "M must be in [1, " + std::to_string(RC_MAX_TIMES) + "]");
     if (!fid && !wsum && !fmin) return fail(RC_EINVAL, "no output requested (fid_out, wsum_out and fmin_out are all NULL)");
     if (wsum && !weights) return fail(RC_EINVAL, "wsum_out needs weights");
-    if (stride && *stride < 0) *stride = K * N * 3;
-    if (stride && *stride != 0 && *stride < K * N * 3) return fail(RC_EINVAL, "draws_ctrl_stride overlaps controllers");
-    if (!stride && !sigma_rows && !(sigma >= 0.0 && sigma < HUGE_VAL))
-        return fail(RC_EINVAL, "sigma must be finite and non-negative (or give sigma_rows)");
-    if (C == 0 || K == 0) {
-        *empty = true;
-        return RC_OK;
-    }
-    if (!ctrl || (stride && !draws)) return fail(RC_EINVAL, "NULL array pointer");
-    if ((C * ((K + 63) / 64)) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
-    return RC_OK;
+    if (int rc = check_draw_stride(N, stride, K)) return rc;
+    return check_draw_source(ctrl, draws, stride, sigma, sigma_rows, C, K, empty);
 }
 
 // what the two kernels' parameter blocks have in common; device pointers, checked arguments
@@ -1730,7 +1733,7 @@ static int enqueue_times(hipStream_t s, int N, int in, int out, const double* h0
     fill_times_params(p, N, in, out, h0_diag, h0_offdiag, ctrl, C, K, M, tscale, tshift, weights, fid, wsum, fmin);
     p.draws = draws;
     p.draw_cstride = draw_cstride;
-    p.align16 = (((uintptr_t)draws & 15) == 0 && (((size_t)draw_cstride * 8) & 15) == 0) ? 1 : 0;
+    p.align16 = draws_align16(draws, draw_cstride);
     const hipError_t e = (hipError_t)rc_times_launch(N, (void*)s, &p);
     if (e != hipSuccess) return fail(RC_EHIP, std::string("rc_times_launch: ") + hipGetErrorString(e));
     return RC_OK;
@@ -1763,9 +1766,8 @@ int rc_mc_fidelity_times_f64(int device, int N, int in, int out, const double* h
     std::lock_guard<std::mutex> lk(g_ctx[device].mu);
     Staging ws;
     if (int rc = get_ctx(device, &ws.ctx)) return rc;
-    const size_t nb_draw = (draws_ctrl_stride == 0 ? (size_t)K * N * 3 : ((size_t)(C - 1) * draws_ctrl_stride + (size_t)K * N * 3)) *
-                           sizeof(double);
-    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_grid = (size_t)M * sizeof(double);
+    const size_t nb_fid = (size_t)C * K * sizeof(double), nb_grid = (size_t)M * sizeof(double),
+                 nb_draw = draws_bytes(C, K, N, draws_ctrl_stride);
     // (an absent grid array stays absent: a slot is declared only for what the caller gave)
     const int s_ctrl = ws.in(controllers, (size_t)C * (N + 1) * sizeof(double)), s_draw = ws.in(draws, nb_draw),
               s_scale = tscale ? ws.in(tscale, nb_grid) : -1, s_shift = tshift ? ws.in(tshift, nb_grid) : -1,
@@ -1803,7 +1805,7 @@ int rc_mc_fidelity_times_philox_f64_async(int device, void* stream, int N, int i
 }
 
 long long rc_stats_times_general_tiles(int device, int reset) {
-    return read_tile_counter(device, reset, rc_times_counter_addr, "reading the readout-time kernels' tile counter failed");
+    return read_unit_counter(device, reset, rc_times_counter_addr, "reading the readout-time kernels' tile counter failed");
 }
 
 int rc_mc_fidelity_sens_philox_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,

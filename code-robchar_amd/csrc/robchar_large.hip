@@ -19,8 +19,7 @@ namespace {
 using rckp::StaticH;
 using rckp::FidParams;
 using rckp::RingRepairList;
-typedef __attribute__((address_space(1))) const void* rc_gptr_t;
-typedef __attribute__((address_space(3))) void* rc_lptr_t;
+#include "tile_stage.inc.h"
 
 #include "k_fidelity_chain.inc.h"
 

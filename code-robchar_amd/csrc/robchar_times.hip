@@ -14,8 +14,7 @@
 namespace {
 
 using rckp::TimesParams;
-typedef __attribute__((address_space(1))) const void* rc_gptr_t;
-typedef __attribute__((address_space(3))) void* rc_lptr_t;
+#include "tile_stage.inc.h"
 
 // tiles in which some sample's QL hit the sweep cap and took the textbook routine (diagnostic; rare path only); counted by
 // mc_fid_times_kernel and mc_fid_times_philox_kernel
