@@ -22,6 +22,144 @@ def _is_torch(x) -> bool:
     return type(x).__module__.startswith("torch")
 
 
+# ---- argument marshalling: each piece of an entry's argument list is made in ONE place, the helpers from here to `_outputs`
+def _np_f64(a, shape=None, name="array"):
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if shape is not None and tuple(a.shape) != tuple(shape):
+        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {a.shape}")
+    return a
+
+
+def _ptr(a):
+    """Address of a NumPy array for the C ABI (None -> NULL)."""
+    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
+
+
+def _dev_ptr(t):
+    """Address of a torch tensor's first element for the C ABI (None -> NULL)."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _on_stream(dev):
+    """(device index, stream) - the two leading arguments of every `*_async` entry: torch's CURRENT stream on `dev`."""
+    import torch
+    return dev.index or 0, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+
+_f64 = None                          # torch.float64 once a CUDA tensor has been seen (this module imports without torch)
+
+
+def _is_dev_f64(t, shape=None) -> bool:
+    """Is `t` a contiguous float64 CUDA tensor (of the shape in this tuple, when one is given)?  (Only a tensor has `is_cuda`.)"""
+    global _f64
+    if not getattr(t, "is_cuda", False):
+        return False
+    if _f64 is None:
+        import torch
+        _f64 = torch.float64
+    return t.dtype == _f64 and t.is_contiguous() and (shape is None or t.shape == shape)
+
+
+def _check_geometry(nspin, inspin, outspin):
+    if not (2 <= int(nspin) <= 32):
+        raise ValueError("Nspin must be in [2, 32]")
+    if not (0 <= int(inspin) < nspin and 0 <= int(outspin) < nspin):
+        raise ValueError("inspin/outspin out of range")
+
+
+def _check_want(want, outputs, allow_empty=False):
+    want = tuple(want)
+    if not (want or allow_empty) or any(w not in outputs for w in want):
+        raise ValueError(f"want: a {'' if allow_empty else 'non-empty '}subset of {outputs}, got {want}")
+    return want
+
+
+def _static_terms(h0_diag, h0_offdiag, nspin):
+    """The static Hamiltonian's (N,) diagonal and (N - 1,) couplings as float64 vectors (None stays None -> NULL)."""
+    return (None if h0_diag is None else _np_f64(h0_diag, (nspin,), "h0_diag"),
+            None if h0_offdiag is None else _np_f64(h0_offdiag, (nspin - 1,), "h0_offdiag"))
+
+
+def _draw_args(controllers, draws, nspin):
+    """A draw tensor beside its controllers -> (draws, C, K, shared, stride): draws (C, K, N, 3), or (1, K, N, 3) with C > 1
+    controllers = ONE set for every controller (`shared`); `stride` is the `draws_ctrl_stride` of the C entries, 0 when shared."""
+    C = controllers.shape[0] if hasattr(controllers, "shape") else len(controllers)
+    if not hasattr(draws, "shape"):
+        draws = np.asarray(draws, dtype=np.float64)
+    shape = draws.shape
+    shared = len(shape) == 4 and shape[0] == 1 and C > 1
+    if len(shape) != 4 or shape != ((1 if shared else C), shape[1], nspin, 3):
+        raise ValueError(f"draws: expected ({C}, K, {nspin}, 3) for the {C} controllers, or (1, K, {nspin}, 3), got {tuple(shape)}")
+    K = shape[1]
+    return draws, C, K, shared, (0 if shared else K * nspin * 3)
+
+
+def _controllers_on(controllers, dev, C, nspin):
+    """The controllers as the contiguous float64 (C, N+1) tensor on `dev` (rows that are not a tensor are uploaded)."""
+    import torch
+    ctrl = controllers if _is_torch(controllers) else torch.as_tensor(np.asarray(controllers, dtype=np.float64))
+    ctrl = ctrl.to(device=dev, dtype=torch.float64).contiguous()
+    if tuple(ctrl.shape) != (C, nspin + 1):
+        raise ValueError(f"controllers: expected ({C}, {nspin + 1}), got {tuple(ctrl.shape)}")
+    return ctrl
+
+
+def _shared_draws_via_torch(call, controllers, draws, device):
+    """A NumPy call with ONE shared (1, K, N, 3) draw set: that form exists on the enqueue path only, so both arrays are uploaded
+    to GPU `device`, `call(controllers, draws)` runs the torch path, and its tensor (or dict of tensors) comes back as NumPy."""
+    import torch
+    dev = torch.device("cuda", device)
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float64)).to(dev)
+    res = call(up(controllers), up(draws))
+    return {k: v.cpu().numpy() for k, v in res.items()} if isinstance(res, dict) else res.cpu().numpy()
+
+
+def _generated_draws_args(controllers, n_draws, sigma, seed, offset, nspin):
+    """The arguments of an entry that generates its draws inside the kernel -> (ctrl, rows, C, K, draw_args): `ctrl` the
+    controllers as a contiguous float64 (C, N+1) CUDA tensor (a NumPy array is uploaded to the current device), `rows` the (C,)
+    per-row scales on its device or None for a float `sigma`, `draw_args` the entry's (seed, offset, sigma, sigma_rows).
+    Everything is validated BEFORE the library is loaded; the caller keeps `ctrl` and `rows` until the entry has returned."""
+    upload = not _is_torch(controllers)
+    if upload:
+        controllers = np.ascontiguousarray(controllers, dtype=np.float64)
+    shape = controllers.shape
+    if len(shape) != 2 or shape[1] != nspin + 1:
+        raise ValueError(f"controllers: expected (C, {nspin + 1}), got {tuple(shape)}")
+    C, K = shape[0], int(n_draws)
+    if K < 0:
+        raise ValueError("n_draws must be non-negative")
+    per_row = not isinstance(sigma, (int, float)) and np.ndim(sigma) > 0
+    if per_row:
+        if not _is_torch(sigma):
+            sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+        if tuple(sigma.shape) != (C,):
+            raise ValueError("sigma: a float or a (C,) tensor")
+    _lib.load()
+    _lib.require_gpu()
+    if upload:                                       # (NumPy rows are uploaded to the current device; the results stay there)
+        import torch
+        controllers = torch.from_numpy(controllers).to(compute_device())
+    if not controllers.is_cuda:
+        raise ValueError("controllers must be a torch CUDA tensor (or a NumPy array, which is uploaded)")
+    ctrl = controllers.double().contiguous()
+    rows = None
+    if per_row:
+        import torch
+        rows = (sigma if _is_torch(sigma) else torch.from_numpy(sigma)).to(device=ctrl.device, dtype=torch.float64).contiguous()
+    return ctrl, rows, C, K, (int(seed) & (2 ** 64 - 1), int(offset), 0.0 if per_row else float(sigma), _dev_ptr(rows))
+
+
+def _outputs(outputs, want, shapes, dev=None, dtypes=None):
+    """Allocate the outputs named in `want` (in that order) with `shapes[name]`: torch tensors on `dev` (float64, or
+    `dtypes[name]`), NumPy float64 arrays for dev = None -> (the dict, the pointers in the order of `outputs`: NULL = not asked for)."""
+    if dev is None:
+        res = {k: np.empty(shapes[k], dtype=np.float64) for k in want}
+        return res, [_ptr(res.get(k)) for k in outputs]
+    import torch
+    res = {k: torch.empty(shapes[k], dtype=(dtypes or {}).get(k, torch.float64), device=dev) for k in want}
+    return res, [_dev_ptr(res.get(k)) for k in outputs]
+
+
 def compute_device():
     """torch.device of the GPU this process computes on: torch's CURRENT device (one process per GPU sets it with
     `torch.cuda.set_device(LOCAL_RANK)`); raises when no GPU is visible (there is no CPU path)."""
@@ -67,30 +205,6 @@ def reduce_packed(fid2d, dkw_eps: float, out=None, overlapped: bool = True):
     return out
 
 
-def _np_f64(a, shape=None, name="array"):
-    a = np.ascontiguousarray(a, dtype=np.float64)
-    if shape is not None and tuple(a.shape) != tuple(shape):
-        raise ValueError(f"{name}: expected shape {tuple(shape)}, got {a.shape}")
-    return a
-
-
-def _ptr(a):
-    return ctypes.c_void_p(a.ctypes.data) if a is not None else None
-
-
-def _small(vec, n, name):
-    if vec is None:
-        return None
-    return _np_f64(vec, (n,), name)
-
-
-def _check_geometry(nspin, inspin, outspin):
-    if not (2 <= int(nspin) <= 32):
-        raise ValueError("Nspin must be in [2, 32]")
-    if not (0 <= int(inspin) < nspin and 0 <= int(outspin) < nspin):
-        raise ValueError("inspin/outspin out of range")
-
-
 def mc_fidelity(controllers, draws, nspin: int, inspin: int, outspin: int, h0_diag=None, h0_offdiag=None,
                 ring: bool = False, device=None, kernel: str = "auto", out=None):
     """Fidelities |<out| exp(-i T H) |in>|^2 for C controllers x K perturbations.
@@ -105,48 +219,31 @@ def mc_fidelity(controllers, draws, nspin: int, inspin: int, outspin: int, h0_di
     lib = _lib.load()
     _lib.require_gpu()
     device = device_index(device)
-    h0d = _small(h0_diag, nspin, "h0_diag")
-    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
     kid = _lib.KERNELS[kernel]
-    n_ctrl_rows = int(controllers.shape[0]) if hasattr(controllers, "shape") else len(controllers)
-    shared = int(draws.shape[0]) == 1 and n_ctrl_rows > 1       # one draw set for every controller
-    if shared and not _is_torch(draws):
-        import torch                                            # the shared form exists on the enqueue path only
-        dev_t = torch.device("cuda", device)
-        res_t = mc_fidelity(torch.as_tensor(np.ascontiguousarray(controllers, dtype=np.float64)).to(dev_t),
-                            torch.as_tensor(np.ascontiguousarray(draws, dtype=np.float64)).to(dev_t), nspin, inspin,
-                            outspin, h0_diag=h0_diag, h0_offdiag=h0_offdiag, ring=ring, kernel=kernel)
-        res_np = res_t.cpu().numpy()
-        if out is not None:
-            out[...] = res_np
-            return out
-        return res_np
+    draws, C, K, shared, stride = _draw_args(controllers, draws, nspin)
     if _is_torch(draws):
         import torch
-        if not (draws.is_cuda and draws.dtype == torch.float64 and draws.is_contiguous()):
+        if not _is_dev_f64(draws):
             raise ValueError("draws must be a contiguous float64 CUDA tensor")
-        C, K = (n_ctrl_rows if shared else int(draws.shape[0])), int(draws.shape[1])
-        if tuple(draws.shape) != ((1 if shared else C), K, nspin, 3):
-            raise ValueError(f"draws: expected (C, K, {nspin}, 3) or (1, K, {nspin}, 3), got {tuple(draws.shape)}")
         dev = draws.device
-        ctrl = controllers if _is_torch(controllers) else torch.as_tensor(np.asarray(controllers, dtype=np.float64))
-        ctrl = ctrl.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(ctrl.shape) != (C, nspin + 1):
-            raise ValueError(f"controllers: expected ({C}, {nspin + 1}), got {tuple(ctrl.shape)}")
+        ctrl = _controllers_on(controllers, dev, C, nspin)
         if out is None:
             out = torch.empty((C, K), dtype=torch.float64, device=dev)
-        elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (C, K)):
+        elif not _is_dev_f64(out, (C, K)):
             raise ValueError("out must be a contiguous float64 CUDA tensor of shape (C, K)")
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rc_mc_fidelity_ex_f64_async(
-            dev.index or 0, ctypes.c_void_p(stream), kid, nspin, inspin, outspin, _ptr(h0d), _ptr(h0o),
-            int(bool(ring)), ctypes.c_void_p(ctrl.data_ptr()), ctypes.c_void_p(draws.data_ptr()),
-            0 if shared else K * nspin * 3, C, K, ctypes.c_void_p(out.data_ptr())))
+        _lib.check(lib.rc_mc_fidelity_ex_f64_async(    # (`_on_stream` spelled out: its call is measurable in bench.py's timed loop)
+            dev.index or 0, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), kid, nspin, inspin, outspin, _ptr(h0d), _ptr(h0o),
+            int(bool(ring)), _dev_ptr(ctrl), _dev_ptr(draws), stride, C, K, _dev_ptr(out)))
         return out
+    if shared:
+        res = _shared_draws_via_torch(lambda c, d: mc_fidelity(c, d, nspin, inspin, outspin, h0_diag=h0_diag, h0_offdiag=h0_offdiag,
+                                                               ring=ring, kernel=kernel), controllers, draws, device)
+        if out is not None:
+            out[...] = res
+            return out
+        return res
     draws = np.ascontiguousarray(draws, dtype=np.float64)
-    if draws.ndim != 4 or draws.shape[2:] != (nspin, 3):
-        raise ValueError(f"draws: expected (C, K, {nspin}, 3), got {draws.shape}")
-    C, K = draws.shape[:2]
     ctrl = _np_f64(controllers, (C, nspin + 1), "controllers")
     res = np.empty((C, K), dtype=np.float64) if out is None else out
     _lib.check(lib.rc_mc_fidelity_kernel_f64(device, kid, nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), int(bool(ring)),
@@ -178,49 +275,42 @@ def mc_fidelity_grad(controllers, draws, nspin: int, inspin: int, outspin: int, 
                                  controllers, draws, nspin, inspin, outspin, h0_diag, h0_offdiag, device, want)
 
 
-def _fidelity_derivatives(which, outputs, shapes_of, controllers, draws, nspin, inspin, outspin, h0_diag, h0_offdiag, device, want):
-    """`mc_fidelity_grad` (which = "grad") and `mc_fidelity_sens` ("sens"): the two C entries take the same arguments and differ
-    in the shape of their second and third output."""
+def _fidelity_derivatives(which, outputs, shapes_of, controllers, draws, nspin, inspin, outspin, h0_diag, h0_offdiag, device, want,
+                          ring_args=(), late_args=None, shared_via_torch=None):
+    """`mc_fidelity_grad` (which = "grad"), `mc_fidelity_sens` ("sens") and `mc_fidelity_times` ("times"): the C entries
+    `rc_mc_fidelity_<which>_f64[_async]` differ in their outputs, in `ring_args`, which the entry takes between `h0_offdiag` and
+    the controllers, and in `late_args(dev)` -> (what it takes between `K` and the outputs for tensors on `dev`, or host arrays
+    for dev = None; whatever has to outlive the call).  `shared_via_torch`: where the blocking entry is not used for one shared
+    draw set, the torch call that takes its place (`_shared_draws_via_torch`).  Geometry, `want`, the static terms and the draws'
+    shape are validated before the library is loaded."""
     _check_geometry(nspin, inspin, outspin)
-    want = tuple(want)
-    if not want or any(w not in outputs for w in want):
-        raise ValueError(f"want: a non-empty subset of {outputs}, got {want}")
+    want = _check_want(want, outputs)
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
+    draws, C, K, shared, stride = _draw_args(controllers, draws, nspin)
     lib = _lib.load()
     _lib.require_gpu()
-    entry_async = getattr(lib, f"rc_mc_fidelity_{which}_f64_async")
-    entry = getattr(lib, f"rc_mc_fidelity_{which}_f64")
     device = device_index(device)
-    h0d = _small(h0_diag, nspin, "h0_diag")
-    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
-    C = int(controllers.shape[0]) if hasattr(controllers, "shape") else len(controllers)
-    if not hasattr(draws, "shape"):
-        draws = np.asarray(draws, dtype=np.float64)
-    shared = int(draws.shape[0]) == 1 and C > 1
-    K = int(draws.shape[1])
-    if tuple(draws.shape) != ((1 if shared else C), K, nspin, 3):
-        raise ValueError(f"draws: expected ({C}, K, {nspin}, 3) or (1, K, {nspin}, 3), got {tuple(draws.shape)}")
-    stride = 0 if shared else K * nspin * 3
-    shapes = shapes_of(C, K, nspin)
+    if late_args is None:
+        late_args = lambda dev: ((), None)           # (the second item: the tensors behind the pointers in the first)
     if _is_torch(draws):
-        import torch
-        if not (draws.is_cuda and draws.dtype == torch.float64 and draws.is_contiguous()):
+        if not _is_dev_f64(draws):
             raise ValueError("draws must be a contiguous float64 CUDA tensor")
         dev = draws.device
-        ctrl = controllers if _is_torch(controllers) else torch.as_tensor(np.asarray(controllers, dtype=np.float64))
-        ctrl = ctrl.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(ctrl.shape) != (C, nspin + 1):
-            raise ValueError(f"controllers: expected ({C}, {nspin + 1}), got {tuple(ctrl.shape)}")
-        res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
-        ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in outputs]
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(entry_async(dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o),
-                               ctypes.c_void_p(ctrl.data_ptr()), ctypes.c_void_p(draws.data_ptr()), stride, C, K, *ptr))
+        ctrl = _controllers_on(controllers, dev, C, nspin)
+        late, keep = late_args(dev)
+        res, out_ptr = _outputs(outputs, want, shapes_of(C, K, nspin), dev)
+        _lib.check(getattr(lib, f"rc_mc_fidelity_{which}_f64_async")(
+            *_on_stream(dev), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), *ring_args, _dev_ptr(ctrl), _dev_ptr(draws), stride, C, K,
+            *late, *out_ptr))
         return res
+    if shared and shared_via_torch is not None:
+        return _shared_draws_via_torch(shared_via_torch, controllers, draws, device)
     draws = np.ascontiguousarray(draws, dtype=np.float64)
     ctrl = _np_f64(controllers, (C, nspin + 1), "controllers")
-    res = {k: np.empty(shapes[k], dtype=np.float64) for k in want}
-    _lib.check(entry(device, nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), _ptr(ctrl), _ptr(draws), stride, C, K,
-                     *[_ptr(res.get(k)) for k in outputs]))
+    late, keep = late_args(None)
+    res, out_ptr = _outputs(outputs, want, shapes_of(C, K, nspin))
+    _lib.check(getattr(lib, f"rc_mc_fidelity_{which}_f64")(
+        device, nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), *ring_args, _ptr(ctrl), _ptr(draws), stride, C, K, *late, *out_ptr))
     return res
 
 
@@ -311,12 +401,23 @@ def _times_want(want, weights, nspin, inspin, outspin):
     _check_geometry(nspin, inspin, outspin)
     if nspin > MAX_NSPIN_TIMES:
         raise ValueError(f"the readout-time kernels support chains of N <= {MAX_NSPIN_TIMES} spins")
-    want = tuple(want)
-    if not want or any(w not in TIMES_OUTPUTS for w in want):
-        raise ValueError(f"want: a non-empty subset of {TIMES_OUTPUTS}, got {want}")
+    want = _check_want(want, TIMES_OUTPUTS)
     if "wsum" in want and weights is None:
         raise ValueError("want 'wsum' needs weights")
     return want
+
+
+def _times_args(a, b, w):
+    """The readout-time entries' own arguments: the outputs' shapes, and the `late_args` between `K` and the outputs - M and the
+    grid's three pointers (NULL weights when absent), host arrays for dev = None, else the grid's tensor on `dev`."""
+    M = len(a)
+
+    def late_args(dev):
+        if dev is None:
+            return (M, _ptr(a), _ptr(b), _ptr(w)), (a, b, w)
+        grid = _times_grid_on_device(a, b, w, dev)
+        return (M, _dev_ptr(grid[0]), _dev_ptr(grid[1]), _dev_ptr(grid[2]) if w is not None else None), grid
+    return (lambda C, K, N: {"fid": (M, C, K), "wsum": (C, K), "min": (C, K)}), late_args
 
 
 def mc_fidelity_times(controllers, draws, nspin: int, inspin: int, outspin: int, tscale=None, tshift=None, weights=None,
@@ -336,52 +437,11 @@ def mc_fidelity_times(controllers, draws, nspin: int, inspin: int, outspin: int,
     row gives NaN in every output."""
     want = _times_want(want, weights, nspin, inspin, outspin)
     a, b, w = _times_grid(tscale, tshift, weights)
-    M = len(a)
-    h0d = _small(h0_diag, nspin, "h0_diag")
-    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
-    C = int(controllers.shape[0]) if hasattr(controllers, "shape") else len(controllers)
-    if not hasattr(draws, "shape"):
-        draws = np.asarray(draws, dtype=np.float64)
-    shared = int(draws.shape[0]) == 1 and C > 1
-    K = int(draws.shape[1])
-    if tuple(draws.shape) != ((1 if shared else C), K, nspin, 3):
-        raise ValueError(f"draws: expected ({C}, K, {nspin}, 3) or (1, K, {nspin}, 3), got {tuple(draws.shape)}")
-    stride = 0 if shared else K * nspin * 3
-    shapes = {"fid": (M, C, K), "wsum": (C, K), "min": (C, K)}
-    lib = _lib.load()
-    _lib.require_gpu()
-    device = device_index(device)
-    if shared and not _is_torch(draws):              # (the shared form through the enqueue path, as in `mc_fidelity`)
-        import torch
-        dev_t = torch.device("cuda", device)
-        res_t = mc_fidelity_times(torch.as_tensor(np.ascontiguousarray(controllers, dtype=np.float64)).to(dev_t),
-                                  torch.as_tensor(np.ascontiguousarray(draws, dtype=np.float64)).to(dev_t), nspin, inspin, outspin,
-                                  tscale=a, tshift=b, weights=w, want=want, h0_diag=h0_diag, h0_offdiag=h0_offdiag)
-        return {k: v.cpu().numpy() for k, v in res_t.items()}
-    if _is_torch(draws):
-        import torch
-        if not (draws.is_cuda and draws.dtype == torch.float64 and draws.is_contiguous()):
-            raise ValueError("draws must be a contiguous float64 CUDA tensor")
-        dev = draws.device
-        ctrl = controllers if _is_torch(controllers) else torch.as_tensor(np.asarray(controllers, dtype=np.float64))
-        ctrl = ctrl.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(ctrl.shape) != (C, nspin + 1):
-            raise ValueError(f"controllers: expected ({C}, {nspin + 1}), got {tuple(ctrl.shape)}")
-        grid = _times_grid_on_device(a, b, w, dev)
-        res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
-        ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in TIMES_OUTPUTS]
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rc_mc_fidelity_times_f64_async(
-            dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), 0, ctypes.c_void_p(ctrl.data_ptr()),
-            ctypes.c_void_p(draws.data_ptr()), stride, C, K, M, ctypes.c_void_p(grid[0].data_ptr()),
-            ctypes.c_void_p(grid[1].data_ptr()), ctypes.c_void_p(grid[2].data_ptr()) if w is not None else None, *ptr))
-        return res
-    draws = np.ascontiguousarray(draws, dtype=np.float64)
-    ctrl = _np_f64(controllers, (C, nspin + 1), "controllers")
-    res = {k: np.empty(shapes[k], dtype=np.float64) for k in want}
-    _lib.check(lib.rc_mc_fidelity_times_f64(device, nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), 0, _ptr(ctrl), _ptr(draws), stride, C,
-                                            K, M, _ptr(a), _ptr(b), _ptr(w), *[_ptr(res.get(k)) for k in TIMES_OUTPUTS]))
-    return res
+    shapes_of, late_args = _times_args(a, b, w)
+    via_torch = lambda c, d: mc_fidelity_times(c, d, nspin, inspin, outspin, tscale=a, tshift=b, weights=w, want=want,
+                                               h0_diag=h0_diag, h0_offdiag=h0_offdiag)
+    return _fidelity_derivatives("times", TIMES_OUTPUTS, shapes_of, controllers, draws, nspin, inspin, outspin, h0_diag, h0_offdiag,
+                                 device, want, ring_args=(0,), late_args=late_args, shared_via_torch=via_torch)
 
 
 def mc_fidelity_times_philox(controllers, n_draws: int, nspin: int, inspin: int, outspin: int, seed: int, offset: int = 0,
@@ -391,45 +451,10 @@ def mc_fidelity_times_philox(controllers, n_draws: int, nspin: int, inspin: int,
     device, the entries named in `want`, enqueued on the current stream; bit-identical to
     `mc_fidelity_times(controllers, philox_normal((C, K, N, 3), seed, scale=sigma, offset=offset), ...)` without that tensor.
     `sigma`: a float, or a (C,) tensor / array (one scale per controller row: every sigma level of an algorithm in one launch)."""
-    import torch
     want = _times_want(want, weights, nspin, inspin, outspin)
-    a, b, w = _times_grid(tscale, tshift, weights)
-    M = len(a)
-    if not _is_torch(controllers):
-        controllers = np.ascontiguousarray(controllers, dtype=np.float64)
-    if controllers.ndim != 2 or int(controllers.shape[1]) != nspin + 1:
-        raise ValueError(f"controllers: expected (C, {nspin + 1}), got {tuple(controllers.shape)}")
-    C, K = int(controllers.shape[0]), int(n_draws)
-    if K < 0:
-        raise ValueError("n_draws must be non-negative")
-    if not _is_torch(sigma) and np.ndim(sigma) > 0:
-        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
-    if np.ndim(sigma) > 0 and tuple(sigma.shape) != (C,):
-        raise ValueError("sigma: a float or a (C,) tensor")
-    h0d = _small(h0_diag, nspin, "h0_diag")
-    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
-    lib = _lib.load()
-    _lib.require_gpu()
-    if not _is_torch(controllers):
-        controllers = torch.from_numpy(controllers).to(compute_device())
-    if not controllers.is_cuda:
-        raise ValueError("controllers must be a torch CUDA tensor (or a NumPy array, which is uploaded)")
-    dev = controllers.device
-    ctrl = controllers.to(dtype=torch.float64).contiguous()
-    rows = None
-    if np.ndim(sigma) > 0:
-        rows = (sigma if _is_torch(sigma) else torch.from_numpy(sigma)).to(device=dev, dtype=torch.float64).contiguous()
-    grid = _times_grid_on_device(a, b, w, dev)
-    shapes = {"fid": (M, C, K), "wsum": (C, K), "min": (C, K)}
-    res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
-    ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in TIMES_OUTPUTS]
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.rc_mc_fidelity_times_philox_f64_async(
-        dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), 0, ctypes.c_void_p(ctrl.data_ptr()),
-        int(seed) & (2 ** 64 - 1), int(offset), 0.0 if rows is not None else float(sigma),
-        ctypes.c_void_p(rows.data_ptr()) if rows is not None else None, C, K, M, ctypes.c_void_p(grid[0].data_ptr()),
-        ctypes.c_void_p(grid[1].data_ptr()), ctypes.c_void_p(grid[2].data_ptr()) if w is not None else None, *ptr))
-    return res
+    shapes_of, late_args = _times_args(*_times_grid(tscale, tshift, weights))
+    return _fidelity_derivatives_philox("times_philox", TIMES_OUTPUTS, shapes_of, controllers, n_draws, nspin, inspin, outspin, seed,
+                                        offset, sigma, h0_diag, h0_offdiag, want, ring_args=(0,), late_args=late_args)
 
 
 def times_general_tiles(device=None, reset: bool = False) -> int:
@@ -456,24 +481,22 @@ def reduce_metrics(fid, q_thresholds=Q_THRESHOLDS, dkw_eps: float = 0.0, want_so
     nq = int(thr.size)
     if _is_torch(fid):
         import torch
-        if not (fid.is_cuda and fid.dtype == torch.float64 and fid.is_contiguous() and fid.dim() == 2):
+        if not (_is_dev_f64(fid) and fid.dim() == 2):
             raise ValueError("fid must be a contiguous float64 CUDA tensor of shape (C, K)")
         C, K = (int(v) for v in fid.shape)
         dev = fid.device
         mk = lambda *s: torch.empty(s, dtype=torch.float64, device=dev)
         if out is not None:          # caller-provided contiguous float64 CUDA buffers (torch path only)
             res = {k: out[k] for k in ("rim1", "std", "min", "q")}
-            assert tuple(res["rim1"].shape) == (3, C) and tuple(res["q"].shape) == (3, max(nq, 1), C)
-            assert all(t.is_cuda and t.is_contiguous() and t.dtype == torch.float64 for t in res.values())
+            assert _is_dev_f64(res["rim1"], (3, C)) and _is_dev_f64(res["q"], (3, max(nq, 1), C))
+            assert _is_dev_f64(res["std"]) and _is_dev_f64(res["min"])
         else:
             res = {"rim1": mk(3, C), "std": mk(3, C), "min": mk(3, C), "q": mk(3, max(nq, 1), C)}
         srt = mk(C, K) if want_sorted else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rc_reduce_ex_f64_async(
-            dev.index or 0, ctypes.c_void_p(stream), ctypes.c_void_p(fid.data_ptr()), C, K, _ptr(thr), nq,
-            float(dkw_eps), ctypes.c_void_p(res["rim1"].data_ptr()), ctypes.c_void_p(res["std"].data_ptr()),
-            ctypes.c_void_p(res["min"].data_ptr()), ctypes.c_void_p(res["q"].data_ptr()),
-            ctypes.c_void_p(srt.data_ptr()) if srt is not None else None, 0 if overlapped else _lib.RC_REDUCE_STANDALONE))
+        _lib.check(lib.rc_reduce_ex_f64_async(         # (`_on_stream` spelled out, as in `mc_fidelity`)
+            dev.index or 0, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _dev_ptr(fid), C, K, _ptr(thr), nq,
+            float(dkw_eps), _dev_ptr(res["rim1"]), _dev_ptr(res["std"]), _dev_ptr(res["min"]), _dev_ptr(res["q"]), _dev_ptr(srt),
+            0 if overlapped else _lib.RC_REDUCE_STANDALONE))
         res["q"] = res["q"][:, :nq]
         if srt is not None:
             res["sorted"] = srt
@@ -500,14 +523,11 @@ def rim_p(fid, p: float, device=None):
     _lib.require_gpu()
     if _is_torch(fid):
         import torch
-        if not (fid.is_cuda and fid.dtype == torch.float64 and fid.is_contiguous() and fid.dim() == 2):
+        if not (_is_dev_f64(fid) and fid.dim() == 2):
             raise ValueError("fid must be a contiguous float64 CUDA tensor of shape (C, K)")
         C, K = (int(v) for v in fid.shape)
         out = torch.empty((C,), dtype=torch.float64, device=fid.device)
-        stream = torch.cuda.current_stream(fid.device).cuda_stream
-        _lib.check(lib.rc_rim_p_f64_async(fid.device.index or 0, ctypes.c_void_p(stream),
-                                          ctypes.c_void_p(fid.data_ptr()), C, K, float(p),
-                                          ctypes.c_void_p(out.data_ptr())))
+        _lib.check(lib.rc_rim_p_f64_async(*_on_stream(fid.device), _dev_ptr(fid), C, K, float(p), _dev_ptr(out)))
         return out
     fid = np.ascontiguousarray(fid, dtype=np.float64)
     C, K = fid.shape
@@ -526,15 +546,14 @@ def philox_normal(shape, seed: int, scale: float = 1.0, offset: int = 0, device=
     if as_torch or out is not None:
         import torch
         if out is not None:
-            if not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and out.numel() == n):
+            if not (_is_dev_f64(out) and out.numel() == n):
                 raise ValueError("out must be a contiguous float64 CUDA tensor with prod(shape) elements")
             dev = out.device
         else:
             dev = torch.device("cuda", device_index(device)) if not hasattr(device, "type") else device
             out = torch.empty(tuple(shape), dtype=torch.float64, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rc_draws_philox_f64_async(dev.index or 0, ctypes.c_void_p(stream), int(seed), int(offset), n,
-                                                 float(scale), ctypes.c_void_p(out.data_ptr())))
+        _lib.check(lib.rc_draws_philox_f64_async(      # (`_on_stream` spelled out, as in `mc_fidelity`)
+            dev.index or 0, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), int(seed), int(offset), n, float(scale), _dev_ptr(out)))
         return out
     out = np.empty(tuple(shape), dtype=np.float64)
     _lib.check(lib.rc_draws_philox_f64(device_index(device), int(seed), int(offset), n, float(scale), _ptr(out)))
@@ -565,6 +584,21 @@ def legacy_stream_usable(rng) -> bool:
             and float(rng.args.get("loc", 0.0)) == 0.0 and legacy_device_exact())
 
 
+def _legacy_state():
+    """numpy's global legacy generator as the `rc_mt19937_state` the device continues."""
+    name, key, pos, has_gauss, cached = np.random.get_state()
+    if name != "MT19937":
+        raise ValueError("numpy's global generator is not the legacy MT19937 stream")
+    st = _lib.Mt19937State()
+    ctypes.memmove(st.key, np.ascontiguousarray(key, dtype=np.uint32).ctypes.data, 624 * 4)
+    st.pos, st.has_gauss, st.gauss = int(pos), int(has_gauss), float(cached)
+    return st
+
+
+def _set_legacy_state(st):
+    np.random.set_state(("MT19937", np.frombuffer(st.key, dtype=np.uint32).copy(), int(st.pos), int(st.has_gauss), float(st.gauss)))
+
+
 def legacy_normal_periods(n_periods: int, period: int, skip: int, scales, out=None, device=None):
     """Continue numpy's global legacy normal stream ON THE GPU (`rc_draws_legacy_f64`): `n_periods` periods of `period`
     draws, the first `skip` of each dropped (burned), the rest scaled by scales[p] -> torch tensor
@@ -580,20 +614,12 @@ def legacy_normal_periods(n_periods: int, period: int, skip: int, scales, out=No
     if out is None:
         dev = torch.device("cuda", device_index(device))
         out = torch.empty((n_periods, period - skip), dtype=torch.float64, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
-              and out.numel() == n_periods * (period - skip)):
+    elif not (_is_dev_f64(out) and out.numel() == n_periods * (period - skip)):
         raise ValueError("out must be a contiguous float64 CUDA tensor with n_periods * (period - skip) elements")
-    name, key, pos, has_gauss, cached = np.random.get_state()
-    if name != "MT19937":
-        raise ValueError("numpy's global generator is not the legacy MT19937 stream")
-    st = _lib.Mt19937State()
-    ctypes.memmove(st.key, np.ascontiguousarray(key, dtype=np.uint32).ctypes.data, 624 * 4)
-    st.pos, st.has_gauss, st.gauss = int(pos), int(has_gauss), float(cached)
-    stream = torch.cuda.current_stream(out.device).cuda_stream
-    _lib.check(lib.rc_draws_legacy_f64(out.device.index or 0, ctypes.c_void_p(stream), ctypes.byref(st), int(n_periods),
-                                       int(period), int(skip), _ptr(scales), ctypes.c_void_p(out.data_ptr())))
-    np.random.set_state(("MT19937", np.frombuffer(st.key, dtype=np.uint32).copy(), int(st.pos), int(st.has_gauss),
-                         float(st.gauss)))
+    st = _legacy_state()
+    _lib.check(lib.rc_draws_legacy_f64(*_on_stream(out.device), ctypes.byref(st), int(n_periods), int(period), int(skip),
+                                       _ptr(scales), _dev_ptr(out)))
+    _set_legacy_state(st)
     return out
 
 
@@ -610,17 +636,10 @@ def directional_draws_device(n: int, ndir: int, sigma: float, device=None):
     ab = torch.empty((n, 2), dtype=torch.float64, device=dev)
     if n == 0:
         return idx, ab
-    name, key, pos, has_gauss, cached = np.random.get_state()
-    if name != "MT19937":
-        raise ValueError("numpy's global generator is not the legacy MT19937 stream")
-    st = _lib.Mt19937State()
-    ctypes.memmove(st.key, np.ascontiguousarray(key, dtype=np.uint32).ctypes.data, 624 * 4)
-    st.pos, st.has_gauss, st.gauss = int(pos), int(has_gauss), float(cached)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.rc_directional_draws_legacy_dev(dev.index or 0, ctypes.c_void_p(stream), ctypes.byref(st), int(n), int(ndir),
-                                                   float(sigma), ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(ab.data_ptr())))
-    np.random.set_state(("MT19937", np.frombuffer(st.key, dtype=np.uint32).copy(), int(st.pos), int(st.has_gauss),
-                         float(st.gauss)))
+    st = _legacy_state()
+    _lib.check(lib.rc_directional_draws_legacy_dev(*_on_stream(dev), ctypes.byref(st), int(n), int(ndir), float(sigma),
+                                                   _dev_ptr(idx), _dev_ptr(ab)))
+    _set_legacy_state(st)
     return idx, ab
 
 
@@ -644,32 +663,21 @@ def mc_fidelity_philox(controllers, n_draws: int, nspin: int, inspin: int, outsp
     `sigma`: a float, or a (C,) float64 CUDA tensor (one scale per controller row)."""
     import torch
     _check_geometry(nspin, inspin, outspin)
-    lib = _lib.load()
-    _lib.require_gpu()
-    if not (_is_torch(controllers) and controllers.is_cuda):
+    if not getattr(controllers, "is_cuda", False):
         raise ValueError("controllers must be a torch CUDA tensor")
-    dev = controllers.device
-    ctrl = controllers.to(dtype=torch.float64).contiguous()
-    C, K = int(ctrl.shape[0]), int(n_draws)
-    if tuple(ctrl.shape) != (C, nspin + 1):
-        raise ValueError(f"controllers: expected ({C}, {nspin + 1})")
+    if getattr(sigma, "ndim", 1) != 1 and _is_torch(sigma):      # (no 0-d tensor read as a float here: that would wait for the device)
+        raise ValueError("sigma: a float or a (C,) tensor")
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
+    ctrl, rows, C, K, draw_args = _generated_draws_args(controllers, n_draws, sigma, seed, offset, nspin)
+    lib = _lib.load()
+    dev = ctrl.device
     if out is None:
         out = torch.empty((C, K), dtype=torch.float64, device=dev)
-    elif not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous() and tuple(out.shape) == (C, K)):
+    elif not _is_dev_f64(out, (C, K)):
         raise ValueError("out must be a contiguous float64 CUDA tensor of shape (C, K)")
-    rows = None
-    if _is_torch(sigma):
-        rows = sigma.to(device=dev, dtype=torch.float64).contiguous()
-        if tuple(rows.shape) != (C,):
-            raise ValueError("sigma: a float or a (C,) tensor")
-    h0d = _small(h0_diag, nspin, "h0_diag")
-    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.rc_mc_fidelity_philox_f64_async(dev.index or 0, ctypes.c_void_p(stream), _lib.KERNELS[kernel], nspin, inspin,
-                                                   outspin, _ptr(h0d), _ptr(h0o), ctypes.c_void_p(ctrl.data_ptr()),
-                                                   int(seed) & (2 ** 64 - 1), int(offset), 0.0 if rows is not None else float(sigma),
-                                                   ctypes.c_void_p(rows.data_ptr()) if rows is not None else None, C, K,
-                                                   ctypes.c_void_p(out.data_ptr())))
+    _lib.check(lib.rc_mc_fidelity_philox_f64_async(    # (`_on_stream` spelled out, as in `mc_fidelity`)
+        dev.index or 0, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream), _lib.KERNELS[kernel], nspin, inspin, outspin,
+        _ptr(h0d), _ptr(h0o), _dev_ptr(ctrl), *draw_args, C, K, _dev_ptr(out)))
     return out
 
 
@@ -688,50 +696,23 @@ def mc_fidelity_sens_philox(controllers, n_draws: int, nspin: int, inspin: int, 
 
 
 def _fidelity_derivatives_philox(which, outputs, shapes_of, controllers, n_draws, nspin, inspin, outspin, seed, offset, sigma,
-                                 h0_diag, h0_offdiag, want, extra_args, late_args=None):
-    """`mc_fidelity_sens_philox` (which = "sens_philox"), `mc_fidelity_grad_philox` ("grad_philox") and `mc_fidelity_grad_listed`
-    ("grad_listed"): the C entries differ in their outputs, in `extra_args`, which the entry takes between `sigma_rows` and `C`,
-    and in `late_args(device)` -> what it takes between `K` and the outputs (tensors are brought to the controllers' device
-    there).  Everything is validated before the library is loaded."""
-    import torch
+                                 h0_diag, h0_offdiag, want, extra_args=(), late_args=None, ring_args=()):
+    """`mc_fidelity_sens_philox` (which = "sens_philox"), `mc_fidelity_grad_philox` ("grad_philox"), `mc_fidelity_grad_listed`
+    ("grad_listed") and `mc_fidelity_times_philox` ("times_philox"): the C entries differ in their outputs, in `ring_args`, which
+    the entry takes between `h0_offdiag` and the controllers, in `extra_args`, which it takes between `sigma_rows` and `C`,
+    and in `late_args(device)` -> (what it takes between `K` and the outputs, with tensors brought to the controllers' device;
+    whatever has to outlive the call).  Everything is validated before the library is loaded."""
     _check_geometry(nspin, inspin, outspin)
-    want = tuple(want)
-    if not want or any(w not in outputs for w in want):
-        raise ValueError(f"want: a non-empty subset of {outputs}, got {want}")
-    if not _is_torch(controllers):
-        controllers = np.ascontiguousarray(controllers, dtype=np.float64)
-    if controllers.ndim != 2 or int(controllers.shape[1]) != nspin + 1:
-        raise ValueError(f"controllers: expected (C, {nspin + 1}), got {tuple(controllers.shape)}")
-    C, K = int(controllers.shape[0]), int(n_draws)
-    if K < 0:
-        raise ValueError("n_draws must be non-negative")
-    if not _is_torch(sigma) and np.ndim(sigma) > 0:
-        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
-    if np.ndim(sigma) > 0 and tuple(sigma.shape) != (C,):
-        raise ValueError("sigma: a float or a (C,) tensor")
-    h0d = _small(h0_diag, nspin, "h0_diag")
-    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
+    want = _check_want(want, outputs)
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
+    ctrl, rows, C, K, draw_args = _generated_draws_args(controllers, n_draws, sigma, seed, offset, nspin)
     lib = _lib.load()
-    _lib.require_gpu()
-    if not _is_torch(controllers):                   # (NumPy rows are uploaded to the current device; the results stay there)
-        controllers = torch.from_numpy(controllers).to(compute_device())
-    if not controllers.is_cuda:
-        raise ValueError("controllers must be a torch CUDA tensor (or a NumPy array, which is uploaded)")
-    dev = controllers.device
-    ctrl = controllers.to(dtype=torch.float64).contiguous()
-    rows = None
-    if np.ndim(sigma) > 0:
-        rows = (sigma if _is_torch(sigma) else torch.from_numpy(sigma)).to(device=dev, dtype=torch.float64).contiguous()
-    shapes = shapes_of(C, K, nspin)
-    res = {k: torch.empty(shapes[k], dtype=torch.float64, device=dev) for k in want}
-    ptr = [(ctypes.c_void_p(res[k].data_ptr()) if k in res else None) for k in outputs]
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    entry = getattr(lib, f"rc_mc_fidelity_{which}_f64_async")
+    dev = ctrl.device
     late, keep = late_args(dev) if late_args is not None else ((), None)     # (`keep`: the tensors behind the pointers in `late`)
-    _lib.check(entry(dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o),
-                     ctypes.c_void_p(ctrl.data_ptr()), int(seed) & (2 ** 64 - 1), int(offset), 0.0 if rows is not None else float(sigma),
-                     ctypes.c_void_p(rows.data_ptr()) if rows is not None else None, *extra_args, C, K, *late, *ptr))
-    del keep
+    res, out_ptr = _outputs(outputs, want, shapes_of(C, K, nspin), dev)
+    _lib.check(getattr(lib, f"rc_mc_fidelity_{which}_f64_async")(
+        *_on_stream(dev), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), *ring_args, _dev_ptr(ctrl), *draw_args, *extra_args, C, K,
+        *late, *out_ptr))
     return res
 
 
@@ -805,7 +786,7 @@ def mc_fidelity_grad_listed(controllers, n_draws: int, listed, weights=None, *, 
         import torch
         lst = (listed if _is_torch(listed) else torch.from_numpy(listed)).to(device=dev).contiguous()
         wts = None if weights is None else (weights if _is_torch(weights) else torch.from_numpy(weights)).to(device=dev).contiguous()
-        return ((ctypes.c_void_p(lst.data_ptr()), ctypes.c_void_p(wts.data_ptr()) if wts is not None else None, L), (lst, wts))
+        return (_dev_ptr(lst), _dev_ptr(wts), L), (lst, wts)
 
     res = _fidelity_derivatives_philox("grad_listed", GRAD_LISTED_OUTPUTS,
                                        lambda C, K, N: {"fid": (C, L), "grad": (C, L, N + 1), "sum": (C, N + 2)},
@@ -842,9 +823,7 @@ def tail_select(fid, alpha: float, want=TAIL_SELECT_OUTPUTS, device=None):
     alpha = float(alpha)
     if not (0.0 < alpha <= 1.0):
         raise ValueError("alpha must be in (0, 1]")
-    want = tuple(want)
-    if any(w not in TAIL_SELECT_OUTPUTS for w in want):
-        raise ValueError(f"want: a subset of {TAIL_SELECT_OUTPUTS}, got {want}")
+    want = _check_want(want, TAIL_SELECT_OUTPUTS, allow_empty=True)
     if fid.ndim != 2:
         raise ValueError("fid: expected (C, K)")
     C, K = (int(v) for v in fid.shape)
@@ -859,20 +838,14 @@ def tail_select(fid, alpha: float, want=TAIL_SELECT_OUTPUTS, device=None):
     if host:
         dev = compute_device() if device is None else torch.device("cuda", device_index(device))
         fid = torch.from_numpy(np.ascontiguousarray(fid, dtype=np.float64)).to(dev)
-    elif not (fid.is_cuda and fid.dtype == torch.float64):
-        raise ValueError("fid must be a float64 CUDA tensor (or a NumPy array, which is uploaded)")
     fid = fid.contiguous()
+    if not _is_dev_f64(fid):
+        raise ValueError("fid must be a float64 CUDA tensor (or a NumPy array, which is uploaded)")
     dev = fid.device
     m = tail_select_len(K, alpha)
-    res = {"list": torch.empty((C, m), dtype=torch.int32, device=dev)}
-    if "weight" in want:
-        res["weight"] = torch.empty((C, m), dtype=torch.float64, device=dev)
-    if "var" in want:
-        res["var"] = torch.empty((C,), dtype=torch.float64, device=dev)
-    ptr = lambda k: ctypes.c_void_p(res[k].data_ptr()) if k in res else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.rc_tail_select_f64_async(dev.index or 0, ctypes.c_void_p(stream), ctypes.c_void_p(fid.data_ptr()), C, K, alpha,
-                                            ptr("list"), ptr("weight"), ptr("var")))
+    res, out_ptr = _outputs(TAIL_SELECT_OUTPUTS, [k for k in TAIL_SELECT_OUTPUTS if k == "list" or k in want],
+                            {"list": (C, m), "weight": (C, m), "var": (C,)}, dev, dtypes={"list": torch.int32})
+    _lib.check(lib.rc_tail_select_f64_async(*_on_stream(dev), _dev_ptr(fid), C, K, alpha, *out_ptr))
     if host:
         return {k: v.cpu().numpy() for k, v in res.items()}
     return res
@@ -899,9 +872,7 @@ def bootstrap_metrics(fid, n_boot: int, seed: int, offset: int = 0, q_thresholds
     bits.  A float64 torch CUDA tensor in: torch tensors on its device, enqueued on the current stream, no host synchronisation.
     A NumPy array in: NumPy arrays out (the blocking entry)."""
     from . import bootstrap as _boot
-    want = tuple(want)
-    if not want or any(w not in BOOTSTRAP_OUTPUTS for w in want):
-        raise ValueError(f"want: a non-empty subset of {BOOTSTRAP_OUTPUTS}, got {want}")
+    want = _check_want(want, BOOTSTRAP_OUTPUTS)
     if route not in BOOTSTRAP_ROUTES:
         raise ValueError(f"route: one of {tuple(BOOTSTRAP_ROUTES)}, got {route!r}")
     if fid.ndim != 2:
@@ -921,36 +892,20 @@ def bootstrap_metrics(fid, n_boot: int, seed: int, offset: int = 0, q_thresholds
     M = 3 + nq
     lib = _lib.load()
     _lib.require_gpu()
-    names = _boot.metric_names(nq)
+    order = ("replicates", "summary")                # (of the C entry's outputs, and of the dict)
+    shapes = {"replicates": (M, C, B), "summary": (M, 4, C)}
+    args = (C, K, B, seed, offset, _ptr(thr) if nq else None, nq, rank_lo, rank_hi, BOOTSTRAP_ROUTES[route])
     if _is_torch(fid):
-        import torch
-        if not (fid.is_cuda and fid.dtype == torch.float64):
-            raise ValueError("fid must be a float64 CUDA tensor (or a NumPy array)")
         fid = fid.contiguous()
-        dev = fid.device
-        res = {}
-        if "replicates" in want:
-            res["replicates"] = torch.empty((M, C, B), dtype=torch.float64, device=dev)
-        if "summary" in want:
-            res["summary"] = torch.empty((M, 4, C), dtype=torch.float64, device=dev)
-        ptr = lambda k: ctypes.c_void_p(res[k].data_ptr()) if k in res else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rc_bootstrap_metrics_f64_async(dev.index or 0, ctypes.c_void_p(stream), ctypes.c_void_p(fid.data_ptr()), C, K, B,
-                                                      seed, offset, _ptr(thr) if nq else None, nq, rank_lo, rank_hi,
-                                                      BOOTSTRAP_ROUTES[route], ptr("replicates"), ptr("summary")))
-        res["names"] = names
-        return res
-    fid = np.ascontiguousarray(fid, dtype=np.float64)
-    res = {}
-    if "replicates" in want:
-        res["replicates"] = np.empty((M, C, B))
-    if "summary" in want:
-        res["summary"] = np.empty((M, 4, C))
-    _lib.check(lib.rc_bootstrap_metrics_f64(device_index(device), _ptr(fid), C, K, B, seed, offset, _ptr(thr) if nq else None, nq,
-                                            rank_lo, rank_hi, BOOTSTRAP_ROUTES[route],
-                                            _ptr(res["replicates"]) if "replicates" in res else None,
-                                            _ptr(res["summary"]) if "summary" in res else None))
-    res["names"] = names
+        if not _is_dev_f64(fid):
+            raise ValueError("fid must be a float64 CUDA tensor (or a NumPy array)")
+        res, out_ptr = _outputs(order, [k for k in order if k in want], shapes, fid.device)
+        _lib.check(lib.rc_bootstrap_metrics_f64_async(*_on_stream(fid.device), _dev_ptr(fid), *args, *out_ptr))
+    else:
+        fid = np.ascontiguousarray(fid, dtype=np.float64)
+        res, out_ptr = _outputs(order, [k for k in order if k in want], shapes)
+        _lib.check(lib.rc_bootstrap_metrics_f64(device_index(device), _ptr(fid), *args, *out_ptr))
+    res["names"] = _boot.metric_names(nq)
     return res
 
 
@@ -979,8 +934,7 @@ def lbfgs_state_len(n_rows: int, ndim: int, m: int) -> int:
 
 
 def _lbfgs_tensor(t, shape, what):
-    import torch
-    if not (_is_torch(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+    if not _is_dev_f64(t, shape):
         raise ValueError(f"{what}: a contiguous float64 CUDA tensor of shape {tuple(shape)}")
     return t
 
@@ -1030,16 +984,11 @@ def lbfgs_init(x0, mask=None, m: int = 5, bounds=None):
         raise _lib.RobCharHipError("rc_lbfgs_state_len disagrees with the state layout of lbfgs.py")
     state = torch.empty((fields, C), dtype=torch.float64, device=dev)
     trial = torch.empty((C, n), dtype=torch.float64, device=dev)
-    stream = torch.cuda.current_stream(dev).cuda_stream
     if bounds is not None:
-        _lib.check(lib.rc_lbfgs_init_box_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, ctypes.c_void_p(x0.data_ptr()),
-                                                   ctypes.c_void_p(mask.data_ptr()) if mask is not None else None,
-                                                   ctypes.c_void_p(lo.data_ptr()), ctypes.c_void_p(hi.data_ptr()),
-                                                   ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(trial.data_ptr())))
-        return state, trial
-    _lib.check(lib.rc_lbfgs_init_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, ctypes.c_void_p(x0.data_ptr()),
-                                           ctypes.c_void_p(mask.data_ptr()) if mask is not None else None,
-                                           ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(trial.data_ptr())))
+        _lib.check(lib.rc_lbfgs_init_box_f64_async(*_on_stream(dev), n, m, C, _dev_ptr(x0), _dev_ptr(mask), _dev_ptr(lo), _dev_ptr(hi),
+                                                   _dev_ptr(state), _dev_ptr(trial)))
+    else:
+        _lib.check(lib.rc_lbfgs_init_f64_async(*_on_stream(dev), n, m, C, _dev_ptr(x0), _dev_ptr(mask), _dev_ptr(state), _dev_ptr(trial)))
     return state, trial
 
 
@@ -1078,22 +1027,12 @@ def lbfgs_advance(state, trial, row_a, row_b=None, *, m: int = 5, kind="one_minu
         lo, hi = _lbfgs_bounds(bounds, trial)
     lib = _lib.load()
     _lib.require_gpu()
-    import torch
-    dev = state.device
-    stream = torch.cuda.current_stream(dev).cuda_stream
+    head = (*_on_stream(state.device), n, m, C, LBFGS_KINDS[kind], float(lam), _dev_ptr(row_a), _dev_ptr(row_b))
+    tail = (float(c1), float(gtol), float(ftol), int(maxiter), int(maxback), _dev_ptr(state), _dev_ptr(trial))
     if bounds is not None:
-        _lib.check(lib.rc_lbfgs_advance_box_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, LBFGS_KINDS[kind], float(lam),
-                                                      ctypes.c_void_p(row_a.data_ptr()),
-                                                      ctypes.c_void_p(row_b.data_ptr()) if row_b is not None else None,
-                                                      ctypes.c_void_p(lo.data_ptr()), ctypes.c_void_p(hi.data_ptr()), float(c1),
-                                                      float(gtol), float(ftol), int(maxiter), int(maxback),
-                                                      ctypes.c_void_p(state.data_ptr()), ctypes.c_void_p(trial.data_ptr())))
-        return
-    _lib.check(lib.rc_lbfgs_advance_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, LBFGS_KINDS[kind], float(lam),
-                                              ctypes.c_void_p(row_a.data_ptr()),
-                                              ctypes.c_void_p(row_b.data_ptr()) if row_b is not None else None, float(c1), float(gtol),
-                                              float(ftol), int(maxiter), int(maxback), ctypes.c_void_p(state.data_ptr()),
-                                              ctypes.c_void_p(trial.data_ptr())))
+        _lib.check(lib.rc_lbfgs_advance_box_f64_async(*head, _dev_ptr(lo), _dev_ptr(hi), *tail))
+    else:
+        _lib.check(lib.rc_lbfgs_advance_f64_async(*head, *tail))
 
 
 LBFGS_RESULT_OUTPUTS = ("x", "f", "grad", "status", "iters", "evals")
@@ -1103,21 +1042,14 @@ def lbfgs_result(state, trial, *, m: int = 5, want=LBFGS_RESULT_OUTPUTS):
     """The rows' results out of the state (`rc_lbfgs_result_f64_async`): dict of torch tensors on the state's device, the entries
     named in `want`: "x" (C, n), "f" (C,), "grad" (C, n) float64, "status" (C,) int32 (0 running, 1 gtol, 2 ftol, 3 maxiter,
     4 line search failed, 5 not finite), "iters" and "evals" (C,) int64.  Enqueue-only, current stream."""
-    want = tuple(want)
-    if not want or any(w not in LBFGS_RESULT_OUTPUTS for w in want):
-        raise ValueError(f"want: a non-empty subset of {LBFGS_RESULT_OUTPUTS}, got {want}")
+    want = _check_want(want, LBFGS_RESULT_OUTPUTS)
     C, n, m = _lbfgs_state_dims(state, trial, m)
     lib = _lib.load()
     _lib.require_gpu()
     import torch
-    dev = state.device
-    shapes = {"x": ((C, n), torch.float64), "f": ((C,), torch.float64), "grad": ((C, n), torch.float64),
-              "status": ((C,), torch.int32), "iters": ((C,), torch.int64), "evals": ((C,), torch.int64)}
-    res = {k: torch.empty(shapes[k][0], dtype=shapes[k][1], device=dev) for k in want}
-    ptr = lambda k: ctypes.c_void_p(res[k].data_ptr()) if k in res else None
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.rc_lbfgs_result_f64_async(dev.index or 0, ctypes.c_void_p(stream), n, m, C, ctypes.c_void_p(state.data_ptr()),
-                                             ptr("x"), ptr("f"), ptr("grad"), ptr("status"), ptr("iters"), ptr("evals")))
+    res, out_ptr = _outputs(LBFGS_RESULT_OUTPUTS, want, {"x": (C, n), "f": (C,), "grad": (C, n), "status": (C,), "iters": (C,), "evals": (C,)},
+                            state.device, dtypes={"status": torch.int32, "iters": torch.int64, "evals": torch.int64})
+    _lib.check(lib.rc_lbfgs_result_f64_async(*_on_stream(state.device), n, m, C, _dev_ptr(state), *out_ptr))
     return res
 
 
@@ -1137,26 +1069,18 @@ def mc_fidelity_directional(controllers, idx, ab, nspin: int, inspin: int, outsp
     C, K = int(controllers.shape[0]), int(n_draws)
     if not (idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous() and idx.numel() == C * K):
         raise ValueError("idx must be a contiguous int32 CUDA tensor with C * K entries")
-    if not (ab.is_cuda and ab.dtype == torch.float64 and ab.is_contiguous() and tuple(ab.shape) == (C * K, 2)
-            and ab.device == dev):
+    if not (_is_dev_f64(ab, (C * K, 2)) and ab.device == dev):
         raise ValueError("ab must be a contiguous float64 CUDA tensor of shape (C * K, 2) on idx's device")
     if controllers.is_cuda and controllers.device != dev:
         raise ValueError("controllers live on another GPU than idx / ab")
-    ctrl = controllers.to(device=dev, dtype=torch.float64).contiguous()
-    if tuple(ctrl.shape) != (C, nspin + 1):
-        raise ValueError(f"controllers: expected ({C}, {nspin + 1})")
+    ctrl = _controllers_on(controllers, dev, C, nspin)
     if out is None:
         out = torch.empty((C, K), dtype=torch.float64, device=dev)
-    elif not (_is_torch(out) and out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()
-              and tuple(out.shape) == (C, K) and out.device == dev):
+    elif not (_is_dev_f64(out, (C, K)) and out.device == dev):
         raise ValueError("out must be a contiguous float64 CUDA tensor of shape (C, K) on idx's device")
-    h0d = _small(h0_diag, nspin, "h0_diag")
-    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.rc_mc_fidelity_directional_f64_async(
-        dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), 0,
-        ctypes.c_void_p(ctrl.data_ptr()), ctypes.c_void_p(idx.data_ptr()), ctypes.c_void_p(ab.data_ptr()), C, K,
-        ctypes.c_void_p(out.data_ptr())))
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
+    _lib.check(lib.rc_mc_fidelity_directional_f64_async(*_on_stream(dev), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), 0,
+                                                        _dev_ptr(ctrl), _dev_ptr(idx), _dev_ptr(ab), C, K, _dev_ptr(out)))
     return out
 
 
@@ -1177,14 +1101,9 @@ def mc_fidelity_nonhermitian(controllers, draws, diag_imag, nspin: int, inspin: 
     if tuple(d.shape) != (C, K, nspin, 3) or tuple(c.shape) != (C, nspin + 1) or (g is not None and tuple(g.shape) != (C, K, nspin)):
         raise ValueError("shapes: controllers (C, N+1), draws (C, K, N, 3), diag_imag (C, K, N)")
     out = torch.empty((C, K), dtype=torch.float64, device=dev)
-    h0d = _small(h0_diag, nspin, "h0_diag")
-    h0o = _small(h0_offdiag, nspin - 1, "h0_offdiag")
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(lib.rc_mc_fidelity_nh_f64_async(dev.index or 0, ctypes.c_void_p(stream), nspin, inspin, outspin, _ptr(h0d),
-                                               _ptr(h0o), int(bool(ring)), ctypes.c_void_p(c.data_ptr()),
-                                               ctypes.c_void_p(d.data_ptr()),
-                                               ctypes.c_void_p(g.data_ptr()) if g is not None else None, C, K,
-                                               ctypes.c_void_p(out.data_ptr())))
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
+    _lib.check(lib.rc_mc_fidelity_nh_f64_async(*_on_stream(dev), nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), int(bool(ring)),
+                                               _dev_ptr(c), _dev_ptr(d), _dev_ptr(g), C, K, _dev_ptr(out)))
     return out.cpu().numpy() if as_numpy else out
 
 
@@ -1262,10 +1181,9 @@ def mc_fidelity_sharded(controllers, draws, nspin: int, inspin: int, outspin: in
     C, K = draws.shape[:2]
     ctrl = _np_f64(controllers, (C, nspin + 1), "controllers")
     res = np.empty((C, K))
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
     _lib.check(lib.rc_mc_fidelity_sharded_f64(ndev, dev_arr, _lib.KERNELS[kernel], nspin, inspin, outspin,
-                                              _ptr(_small(h0_diag, nspin, "h0_diag")),
-                                              _ptr(_small(h0_offdiag, nspin - 1, "h0_offdiag")), int(bool(ring)),
-                                              _ptr(ctrl), _ptr(draws), C, K, _ptr(res)))
+                                              _ptr(h0d), _ptr(h0o), int(bool(ring)), _ptr(ctrl), _ptr(draws), C, K, _ptr(res)))
     return res
 
 
@@ -1289,10 +1207,9 @@ def mc_metrics_sharded(controllers, n_draws: int, nspin: int, inspin: int, outsp
     nq = int(thr.size)
     res = {"rim1": np.empty((3, C)), "std": np.empty((3, C)), "min": np.empty((3, C)), "q": np.empty((3, nq, C))}
     fid = np.empty((C, K)) if want_fid else None
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
     _lib.check(lib.rc_mc_metrics_sharded_f64(ndev, dev_arr, _lib.KERNELS[kernel], nspin, inspin, outspin,
-                                             _ptr(_small(h0_diag, nspin, "h0_diag")),
-                                             _ptr(_small(h0_offdiag, nspin - 1, "h0_offdiag")), int(bool(ring)),
-                                             _ptr(ctrl), _ptr(draws), int(seed), int(offset), float(sigma), C, K,
+                                             _ptr(h0d), _ptr(h0o), int(bool(ring)), _ptr(ctrl), _ptr(draws), int(seed), int(offset), float(sigma), C, K,
                                              _ptr(thr), nq, float(dkw_eps), _ptr(res["rim1"]), _ptr(res["std"]),
                                              _ptr(res["min"]), _ptr(res["q"]) if nq else None, _ptr(fid)))
     if want_fid:
@@ -1359,10 +1276,10 @@ def mc_metrics_gathered(comm: "RcclComm", controllers, n_draws: int, nspin: int,
         cmax = -(-C // comm.ndev)
         for d in comm.devices:                        # rank r's receive buffer lives on GPU devices[r]
             keep.append(torch.empty((comm.ndev * cmax * K,), dtype=torch.float64, device=torch.device("cuda", d)))
-        fid_dev = (ctypes.c_void_p * comm.ndev)(*[t.data_ptr() for t in keep])
+        fid_dev = (ctypes.c_void_p * comm.ndev)(*[_dev_ptr(t) for t in keep])
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
     _lib.check(lib.rc_mc_metrics_gathered_f64(comm.handle, _lib.KERNELS[kernel], nspin, inspin, outspin,
-                                              _ptr(_small(h0_diag, nspin, "h0_diag")), _ptr(_small(h0_offdiag, nspin - 1, "h0_offdiag")),
-                                              int(bool(ring)), _ptr(ctrl), _ptr(draws), int(seed), int(offset), float(sigma), C, K,
+                                              _ptr(h0d), _ptr(h0o), int(bool(ring)), _ptr(ctrl), _ptr(draws), int(seed), int(offset), float(sigma), C, K,
                                               _ptr(thr), nq, float(dkw_eps), None, fid_dev, _ptr(table), _ptr(fid)))
     res = {"rim1": table[0:3].copy(), "std": table[3:6].copy(), "min": table[6:9].copy(),
            "q": table[9:].reshape(3, nq, C).copy()}
