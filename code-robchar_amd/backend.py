@@ -741,6 +741,36 @@ def mc_fidelity_grad_philox(controllers, n_draws: int, nspin: int, inspin: int, 
                                         (int(bool(shared)),))
 
 
+def mc_fidelity_grad_times_philox(controllers, n_draws: int, nspin: int, inspin: int, outspin: int, seed: int, offset: int = 0,
+                                  sigma=0.05, shared: bool = False, tscale=None, tshift=None, weights=None, h0_diag=None,
+                                  h0_offdiag=None, want=GRAD_PHILOX_OUTPUTS):
+    """`mc_fidelity_grad_philox` on a GRID OF READOUT TIMES from ONE eigen decomposition per sample
+    (`rc_mc_fidelity_grad_times_philox_f64_async`): with u_cj = T_c tscale_j + tshift_j (|u_cj| = `readout_times`) and the
+    weights w_j, per sample W = sum_j w_j F(u_cj) and its gradient with respect to the controller row,
+
+        "fid" (C, K) = W, "grad" (C, K, N+1) = dW/dx  (the time entry: sum_j w_j tscale_j sgn(u_cj) F'(|u_cj|)),
+        "mean" (C, N+2) = (mean W, mean dW/dx), "moment" (C, N+2) = (mean W^2, mean W dW/dx)   (`noise.moments_from_sums`),
+
+    the entries named in `want`, torch tensors on the controllers' device, enqueued on the current stream.  `tscale`, `tshift`:
+    (M,) arrays, absent = all 1 / all 0; `weights`: (M,), required; 1 <= M <= 64 - `noise.readout_jitter_nodes` makes the grid of
+    Gaussian readout jitter.  The grid is uploaded once per distinct grid.  "fid" and "grad" are bit for bit what M calls of
+    `mc_fidelity_grad_philox` on controllers with the time entry u_cj give, the time column multiplied by tscale_j and the slabs
+    combined by acc = w_0 v_0; acc = fma(w_j, v_j, acc).  Draw modes, `sigma`, NaN rows, N <= `max_nspin_grad()`: as there."""
+    if weights is None:
+        raise ValueError("weights: required (one per grid time)")
+    a, b, w = _times_grid(tscale, tshift, weights)
+    M = len(a)
+
+    def late_args(dev):
+        grid = _times_grid_on_device(a, b, w, dev)
+        return (M, _dev_ptr(grid[0]), _dev_ptr(grid[1]), _dev_ptr(grid[2])), grid
+
+    return _fidelity_derivatives_philox("grad_times_philox", GRAD_PHILOX_OUTPUTS,
+                                        lambda C, K, N: {"fid": (C, K), "grad": (C, K, N + 1), "mean": (C, N + 2), "moment": (C, N + 2)},
+                                        controllers, n_draws, nspin, inspin, outspin, seed, offset, sigma, h0_diag, h0_offdiag, want,
+                                        (int(bool(shared)),), late_args)
+
+
 GRAD_LISTED_OUTPUTS = ("fid", "grad", "sum")
 
 

@@ -111,6 +111,31 @@ struct GradPhiloxParams {
     StaticH h0;
 };
 
+// GradPhiloxParams on a grid of M readout times (k_fidelity_grad_times_philox.inc.h): u_cj = T_c tscale_j + tshift_j; `fid` and
+// `grad` carry the weighted sums W = sum_j weights_j F_j and dW/dx, the part rows their tile sums (and, with `moments`, those of
+// W^2 and W dW/dx).
+struct GradTimesParams {
+    const double* ctrl;    // [C][N+1]
+    double* fid;           // [C][K] or NULL: W
+    double* grad;          // [C][K][N+1] or NULL: dW/dx
+    double* part;          // [ntiles][N+2] per-tile sums for the row means ([ntiles][2N+4] with `moments`), or NULL
+    long long C, K;
+    long long tiles_per_ctrl;
+    long long ntiles;
+    int in, out;
+    int shared;                       // 1: one draw set for every controller row
+    int moments;                      // 1: the part rows also carry the sums of W^2 and W dW/dx
+    unsigned long long seed;
+    unsigned long long offset;        // stream element of sample (c = 0, k = 0), site 0, slot 0
+    const double* sigma_rows;         // [C] scale per controller row, or NULL: `sigma` for all
+    double sigma;
+    const double* tscale;  // [M] or NULL: 1
+    const double* tshift;  // [M] or NULL: 0
+    const double* weights; // [M]
+    int M;
+    StaticH h0;
+};
+
 // GradPhiloxParams over a list of each row's draws (k_fidelity_grad_listed.inc.h): slot s of row c is sample (c, list[c][s]) of
 // the same stream convention - a value outside 0 .. K - 1 is an empty slot -; the tiles cover the L slots of a row, the outputs
 // are per slot and the part rows carry the sums weighted by weight[c][s].

@@ -1,6 +1,7 @@
 // librobchar_hip.so, third translation unit: the fidelity-gradient kernels (k_fidelity_grad.inc.h, N = 2 .. RC_MAX_NSPIN_GRAD)
 // and the noise-sensitivity kernels (k_fidelity_sens.inc.h; k_fidelity_sens_philox.inc.h: the same with the counter-based draws
-// generated inside the kernel; same range), and the gradient kernel that generates its draws (k_fidelity_grad_philox.inc.h),
+// generated inside the kernel; same range), the gradient kernel that generates its draws (k_fidelity_grad_philox.inc.h) and
+// that kernel on a grid of readout times (k_fidelity_grad_times_philox.inc.h),
 // compiled in parallel with robchar_hip.hip and robchar_large.hip (`make -j`).  The host side and the C ABI are in
 // robchar_hip.hip, which reaches the launches below through hidden entry points.
 #include <hip/hip_runtime.h>
@@ -11,6 +12,7 @@
 #include "../../include/robchar_hip.h"
 #include "kernel_params.h"
 #include "grad_core.h"
+#include "grad_times_core.h"
 #include "sens_core.h"
 
 namespace {
@@ -18,12 +20,13 @@ namespace {
 using rckp::GradParams;
 using rckp::GradPhiloxParams;
 using rckp::GradListedParams;
+using rckp::GradTimesParams;
 using rckp::SensParams;
 using rckp::SensPhiloxParams;
 #include "tile_stage.inc.h"
 
 // tiles in which some sample's QL hit the sweep cap and took the textbook routine (diagnostic; rare path only); counted by
-// mc_fid_grad_kernel, mc_fid_grad_philox_kernel and mc_fid_grad_listed_kernel
+// mc_fid_grad_kernel, mc_fid_grad_philox_kernel, mc_fid_grad_times_philox_kernel and mc_fid_grad_listed_kernel
 __device__ unsigned long long g_grad_general_tiles = 0;
 
 // the same for mc_fid_sens_kernel and mc_fid_sens_philox_kernel
@@ -34,6 +37,7 @@ __device__ unsigned long long g_sens_general_tiles = 0;
 #include "philox_core.inc.h"
 #include "k_fidelity_sens_philox.inc.h"
 #include "k_fidelity_grad_philox.inc.h"
+#include "k_fidelity_grad_times_philox.inc.h"
 #include "k_fidelity_grad_listed.inc.h"
 
 }  // namespace
@@ -57,6 +61,7 @@ RC_LAUNCH_2_TO_12(launch_sens, mc_fid_sens_kernel, rckp::SensParams)
 RC_LAUNCH_2_TO_12(launch_sens_philox, mc_fid_sens_philox_kernel, rckp::SensPhiloxParams)
 RC_LAUNCH_2_TO_12(launch_grad_philox, mc_fid_grad_philox_kernel, rckp::GradPhiloxParams)
 RC_LAUNCH_2_TO_12(launch_grad_listed, mc_fid_grad_listed_kernel, rckp::GradListedParams)
+RC_LAUNCH_2_TO_12(launch_grad_times_philox, mc_fid_grad_times_philox_kernel, rckp::GradTimesParams)
 #undef RC_LAUNCH_2_TO_12
 #undef RC_LAUNCH_CASE
 
@@ -93,6 +98,12 @@ __attribute__((visibility("hidden"))) int rc_sens_philox_launch(int N, void* s, 
 __attribute__((visibility("hidden"))) int rc_grad_philox_launch(int N, void* s, const rckp::GradPhiloxParams* p, double* mean,
                                                                 double* moment) {
     return launch_row_means(launch_grad_philox(N, (hipStream_t)s, *p), (hipStream_t)s, p->part, mean, moment, p->moments != 0,
+                            N + 2, p->tiles_per_ctrl, p->K, p->C);
+}
+// (the same second pass: the part rows carry the sums of W, dW/dx and - p->moments - of W^2, W dW/dx)
+__attribute__((visibility("hidden"))) int rc_grad_times_philox_launch(int N, void* s, const rckp::GradTimesParams* p, double* mean,
+                                                                      double* moment) {
+    return launch_row_means(launch_grad_times_philox(N, (hipStream_t)s, *p), (hipStream_t)s, p->part, mean, moment, p->moments != 0,
                             N + 2, p->tiles_per_ctrl, p->K, p->C);
 }
 

@@ -71,6 +71,8 @@ __attribute__((visibility("hidden"))) int rc_large_counter_addr(int which, void*
 __attribute__((visibility("hidden"))) int rc_grad_launch(int N, void* stream, const rckp::GradParams* p, double* mean);
 __attribute__((visibility("hidden"))) int rc_grad_philox_launch(int N, void* stream, const rckp::GradPhiloxParams* p, double* mean,
                                                                 double* moment);
+__attribute__((visibility("hidden"))) int rc_grad_times_philox_launch(int N, void* stream, const rckp::GradTimesParams* p, double* mean,
+                                                                      double* moment);
 __attribute__((visibility("hidden"))) int rc_grad_listed_launch(int N, void* stream, const rckp::GradListedParams* p, double* sum);
 __attribute__((visibility("hidden"))) int rc_grad_counter_addr(void** addr);
 __attribute__((visibility("hidden"))) int rc_sens_launch(int N, void* stream, const rckp::SensParams* p, double* mean);
@@ -1854,6 +1856,39 @@ int rc_mc_fidelity_grad_philox_f64_async(int device, void* stream, int N, int in
     p.sigma = sigma;
     return launch_with_part(s, p, mean_out_dev || moment_out_dev, (N + 2) * (p.moments ? 2 : 1), "rc_grad_philox_launch",
                             [&] { return rc_grad_philox_launch(N, (void*)s, &p, mean_out_dev, moment_out_dev); });
+}
+
+int rc_mc_fidelity_grad_times_philox_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,
+                                               const double* h0_offdiag, const double* controllers_dev, unsigned long long seed,
+                                               unsigned long long offset, double sigma, const double* sigma_rows_dev,
+                                               int shared_draws, long long C, long long K, int M, const double* tscale_dev,
+                                               const double* tshift_dev, const double* weights_dev, double* wfid_out_dev,
+                                               double* wgrad_out_dev, double* mean_out_dev, double* moment_out_dev) {
+    bool empty = false;
+    if (int rc = check_deriv_args("fidelity-gradient", "wfid_out, wgrad_out, mean_out and moment_out", N, in, out, controllers_dev,
+                                  nullptr, nullptr, sigma, sigma_rows_dev, C, K,
+                                  wfid_out_dev || wgrad_out_dev || mean_out_dev || moment_out_dev, &empty))
+        return rc;
+    if (M < 1 || M > RC_MAX_TIMES) return fail(RC_EINVAL, "M must be in [1, " + std::to_string(RC_MAX_TIMES) + "]");
+    if (!weights_dev) return fail(RC_EINVAL, "NULL array pointer (weights)");
+    if (empty) return RC_OK;
+    RC_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    rckp::GradTimesParams p{};
+    fill_deriv_params(p, N, in, out, h0_diag, h0_offdiag, controllers_dev, C, K, wfid_out_dev);
+    p.grad = wgrad_out_dev;
+    p.shared = shared_draws ? 1 : 0;
+    p.moments = moment_out_dev ? 1 : 0;
+    p.seed = seed;
+    p.offset = offset;
+    p.sigma_rows = sigma_rows_dev;
+    p.sigma = sigma;
+    p.tscale = tscale_dev;
+    p.tshift = tshift_dev;
+    p.weights = weights_dev;
+    p.M = M;
+    return launch_with_part(s, p, mean_out_dev || moment_out_dev, (N + 2) * (p.moments ? 2 : 1), "rc_grad_times_philox_launch",
+                            [&] { return rc_grad_times_philox_launch(N, (void*)s, &p, mean_out_dev, moment_out_dev); });
 }
 
 int rc_mc_fidelity_grad_listed_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,

@@ -429,14 +429,10 @@ class noise_model_base:
         return {"fav": mean[:, 0].copy(), "dfav_dlogsigma": mean[:, 1].copy(),
                 "direction": mean[:, 2:].reshape(-1, self.Nspin, 3).copy()}
 
-    def fidelity_moments_philox(self, controllers, n_draws: int, seed: int, sigma=None, offset: int = 0, shared: bool = False):
-        """Mean, variance and standard deviation of the fidelity over `n_draws` counter-based draws per controller generated
-        INSIDE the gradient kernel, with their gradients with respect to the controller: `moments_from_sums` of the "mean" and
-        "moment" rows of ONE `backend.mc_fidelity_grad_philox` launch (no per-sample output, no draw tensor).  NumPy arrays out.
-        `sigma`: None = the model's current level; a float; or one value per controller row.  shared=False: row c, draw k, site
-        i, slot s is stream element offset + ((c K + k) N + i) 3 + s; shared=True (common random numbers: the same draws for
-        every controller, the `fidelity_ss_av` kind of objective): offset + (k N + i) 3 + s.  Chain topology with real static
-        couplings only."""
+    def _moments_of_one_launch(self, launch, controllers, n_draws, seed, sigma, offset, shared):
+        """`moments_from_sums` of the "mean" and "moment" rows of one launch of `launch` - `backend.mc_fidelity_grad_philox` or one
+        that takes its arguments - with the model's static terms; what `fidelity_moments_philox` and
+        `fidelity_jitter_moments_philox` share.  NumPy arrays out."""
         diag, off, ring, imag = self._static_terms()
         if ring:
             raise NotImplementedError("the fidelity gradient is implemented for the chain topology only")
@@ -447,10 +443,47 @@ class noise_model_base:
             sigma = float(self.rng.args.get("scale", self.noise))
         if not backend._is_torch(controllers):
             controllers = np.asarray(controllers, dtype=np.float64).reshape(-1, self.Nspin + 1)
-        res = backend.mc_fidelity_grad_philox(controllers, int(n_draws), self.Nspin, self.inspin, self.outspin, seed, offset=offset,
-                                              sigma=sigma, shared=shared, h0_diag=diag, h0_offdiag=off, want=("mean", "moment"))
+        res = launch(controllers, int(n_draws), self.Nspin, self.inspin, self.outspin, seed, offset=offset, sigma=sigma, shared=shared,
+                     h0_diag=diag, h0_offdiag=off, want=("mean", "moment"))
         mean, moment = (v.cpu().numpy() if backend._is_torch(v) else np.asarray(v) for v in (res["mean"], res["moment"]))
         return {k: v.copy() for k, v in moments_from_sums(mean, moment).items()}
+
+    def fidelity_moments_philox(self, controllers, n_draws: int, seed: int, sigma=None, offset: int = 0, shared: bool = False):
+        """Mean, variance and standard deviation of the fidelity over `n_draws` counter-based draws per controller generated
+        INSIDE the gradient kernel, with their gradients with respect to the controller: `moments_from_sums` of the "mean" and
+        "moment" rows of ONE `backend.mc_fidelity_grad_philox` launch (no per-sample output, no draw tensor).  NumPy arrays out.
+        `sigma`: None = the model's current level; a float; or one value per controller row.  shared=False: row c, draw k, site
+        i, slot s is stream element offset + ((c K + k) N + i) 3 + s; shared=True (common random numbers: the same draws for
+        every controller, the `fidelity_ss_av` kind of objective): offset + (k N + i) 3 + s.  Chain topology with real static
+        couplings only."""
+        return self._moments_of_one_launch(backend.mc_fidelity_grad_philox, controllers, n_draws, seed, sigma, offset, shared)
+
+    def fidelity_jitter_moments_philox(self, controllers, n_draws: int, seed: int, sigma_t: float, order: int = 8, sigma=None,
+                                       offset: int = 0, shared: bool = False):
+        """`fidelity_moments_philox` of the fidelity AVERAGED OVER A GAUSSIAN READOUT-TIME JITTER of standard deviation `sigma_t`:
+        with W = E_delta F(T + delta) by the `order`-point Gauss-Hermite rule of `readout_jitter_nodes`, the mean, variance and
+        standard deviation of W over the draws and their gradients with respect to the controller (the time entry included) -
+        `moments_from_sums` of the "mean" and "moment" rows of ONE `backend.mc_fidelity_grad_times_philox` launch, one eigen
+        decomposition per sample for the whole rule.  The same dict as `fidelity_moments_philox`; the other arguments as there."""
+        tshift, weights = readout_jitter_nodes(sigma_t, order)
+
+        def launch(*args, **kw):
+            return backend.mc_fidelity_grad_times_philox(*args, tshift=tshift, weights=weights, **kw)
+        return self._moments_of_one_launch(launch, controllers, n_draws, seed, sigma, offset, shared)
+
+    @staticmethod
+    def _jitter_grid(jitter):
+        """`optimize_controllers`' `jitter` as the grid keywords of `backend.mc_fidelity_grad_times_philox`: sigma_t, (sigma_t,
+        order) - the Gauss-Hermite rule of `readout_jitter_nodes` - or dict(tscale=, tshift=, weights=) taken as it is"""
+        if isinstance(jitter, dict):
+            unknown = set(jitter) - {"tscale", "tshift", "weights"}
+            if unknown or jitter.get("weights") is None:
+                raise ValueError("jitter: dict(tscale=, tshift=, weights=) with weights")
+            tscale, tshift, weights = backend._times_grid(jitter.get("tscale"), jitter.get("tshift"), jitter["weights"])
+            return {"tscale": tscale, "tshift": tshift, "weights": weights}      # (host vectors: nothing is converted per evaluation)
+        sigma_t, order = (jitter if isinstance(jitter, (tuple, list)) else (jitter, 8))
+        tshift, weights = readout_jitter_nodes(float(sigma_t), int(order))
+        return {"tscale": None, "tshift": tshift, "weights": weights}
 
     def _cvar_device(self, ctrl, K: int, seed: int, alpha: float, sigma, offset: int, shared: bool, diag, off):
         """The device-resident part of `fidelity_cvar_philox`: ctrl (C, N+1) float64 CUDA tensor, `sigma` a float or a (C,) tensor
@@ -517,7 +550,8 @@ class noise_model_base:
         return {"cvar": total[:, 0].copy(), "grad_cvar": total[:, 1:].copy(), "var": var}
 
     def optimize_controllers(self, controllers, n_draws: int, seed: int, objective="mean", sigma=None, offset: int = 0,
-                             shared: bool = True, mask=None, max_evals: int = 60, poll: int = 8, bounds=None, **lbfgs_params):
+                             shared: bool = True, mask=None, max_evals: int = 60, poll: int = 8, bounds=None, jitter=None,
+                             **lbfgs_params):
         """Robust re-optimisation of ALL controller rows at once by the batched L-BFGS state machine on the device
         (`backend.lbfgs_init` / `lbfgs_advance`; the definition is `lbfgs.py`): per evaluation ONE gradient launch over the rows'
         trial points and one advance launch, everything device-resident on the current stream.  Objective, over `n_draws`
@@ -526,6 +560,12 @@ class noise_model_base:
             "mean"             1 - mean F                        `mc_fidelity_grad_philox`, want = ("mean",)
             ("std", lam)       1 - mean F + lam std F            ... want = ("mean", "moment")
             ("cvar", alpha)    1 - CVaR_alpha F                  the three launches of `fidelity_cvar_philox`
+
+        `jitter` (None = off: exactly the launches above): sigma_t, (sigma_t, order) or dict(tscale=, tshift=, weights=) - F is
+        replaced by W = E_delta F(T + delta), its average over a Gaussian readout-time jitter of standard deviation sigma_t (the
+        Gauss-Hermite rule of `readout_jitter_nodes`, order 8 by default) or over the given grid, and the "mean" and ("std", lam)
+        objectives are evaluated by ONE `mc_fidelity_grad_times_philox` launch per evaluation (one eigen decomposition per sample
+        for the whole grid; the grid goes to the device once).  ("cvar", alpha) with `jitter`: NotImplementedError.
 
         shared=True (common random numbers, the default): every row and every evaluation sees the same draws, so the objective is
         a deterministic function of the controller - what a line search needs.  `mask` (C, N+1) of 0 / 1 or None: a masked entry
@@ -551,6 +591,11 @@ class noise_model_base:
                 raise ValueError("alpha must be in (0, 1]")
         else:
             raise ValueError('objective: "mean", ("std", lam) or ("cvar", alpha)')
+        grid = None
+        if jitter is not None:
+            if kind == "cvar":
+                raise NotImplementedError("the CVaR objective under readout jitter (the listed-sample kernel has no time grid)")
+            grid = self._jitter_grid(jitter)
         K, N = int(n_draws), self.Nspin
         if K < 1 or int(max_evals) < 1 or int(poll) < 1:
             raise ValueError("n_draws, max_evals and poll must be positive")
@@ -590,8 +635,12 @@ class noise_model_base:
                 row_a, _ = self._cvar_device(trial, K, seed, par, sigma, offset, shared, diag, off)
             else:
                 want = ("mean", "moment") if kind == "one_minus_plus_std" else ("mean",)
-                res = backend.mc_fidelity_grad_philox(trial, K, N, self.inspin, self.outspin, seed, offset=offset, sigma=sigma,
-                                                      shared=shared, want=want, **geo)
+                if grid is None:
+                    res = backend.mc_fidelity_grad_philox(trial, K, N, self.inspin, self.outspin, seed, offset=offset, sigma=sigma,
+                                                          shared=shared, want=want, **geo)
+                else:                                                 # (the grid's device copy is made at the first evaluation)
+                    res = backend.mc_fidelity_grad_times_philox(trial, K, N, self.inspin, self.outspin, seed, offset=offset,
+                                                                sigma=sigma, shared=shared, want=want, **grid, **geo)
                 row_a, row_b = res["mean"], res.get("moment")
             backend.lbfgs_advance(state, trial, row_a, row_b, m=m, kind="one_minus" if kind == "cvar" else kind, lam=par,
                                   **box, **lbfgs_params)

@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 16     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 17     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -73,7 +73,8 @@ extern "C" {
                                   14: + rc_lbfgs_init_box_f64_async, rc_lbfgs_advance_box_f64_async (additive);
                                   15: + rc_bootstrap_metrics_f64_async, rc_bootstrap_metrics_f64 (additive);
                                   16: + rc_mc_fidelity_times_f64_async, rc_mc_fidelity_times_f64,
-                                      rc_mc_fidelity_times_philox_f64_async, rc_stats_times_general_tiles, RC_MAX_TIMES (additive) */
+                                      rc_mc_fidelity_times_philox_f64_async, rc_stats_times_general_tiles, RC_MAX_TIMES (additive);
+                                  17: + rc_mc_fidelity_grad_times_philox_f64_async (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -502,6 +503,35 @@ int rc_mc_fidelity_times_philox_f64_async(int device, void* stream, int N, int i
                                           const double* weights_dev, double* fid_out_dev, double* wsum_out_dev, double* fmin_out_dev);
 /* Diagnostic (ABI 16): the counter of rc_stats_grad_general_tiles for the two readout-time kernels. */
 long long rc_stats_times_general_tiles(int device, int reset);
+
+/* (ABI 17) rc_mc_fidelity_grad_philox_f64_async ON A GRID OF READOUT TIMES, from ONE eigen decomposition per sample: the weighted
+ * fidelity over the grid and its gradient with respect to the controller row - the objective 1 - E_draws E_delta F(T + delta) of a
+ * controller under readout-time jitter, and its moment sums, in one launch.  The grid is that of rc_mc_fidelity_times_f64_async:
+ * M times, 1 <= M <= RC_MAX_TIMES, tscale_dev [M] and tshift_dev [M] (NULL = all 1 / all 0), weights_dev [M] (required).  For
+ * controller row c with time entry T_c (signed, as stored)
+ *     u_cj = T_c tscale_j + tshift_j        (the product rounded first, the sum second; |u_cj| is the t_cj of the times entries),
+ *     W(c, k)   = sum_j w_j F_j(c, k),      dW/dx_l = sum_j w_j dF_j/dx_l           for the N biases,
+ *     dW/dx_N   = sum_j w_j tscale_j sgn(u_cj) F_j'(|u_cj|)                         (a time with u_cj = 0 contributes 0),
+ * the grid and the weights being constants of the objective.  Per time the sample's F_j and gradient are those of
+ * rc_mc_fidelity_grad_philox_f64_async for a controller whose time entry is u_cj, the time entry then multiplied by tscale_j
+ * (rounded once); every sum is  acc = w_0 v_0; acc = fma(w_j, v_j, acc), j = 1 .. M - 1.  So wfid_out and wgrad_out are BIT FOR BIT
+ * what M launches of that entry, the scaling of the time column and that fma sequence give, and with M = 1, the unit grid and
+ * w = 1 all four outputs are that entry's bits.
+ * Outputs, each optional (NULL = not wanted; all four NULL: RC_EINVAL):
+ *     wfid_out [C][K] = W, wgrad_out [C][K][N+1] = dW/dx, mean_out [C][N+2] = (mean W, mean dW/dx),
+ *     moment_out [C][N+2] = (mean W^2, mean W dW/dx_0 .. mean W dW/dx_N): as in rc_mc_fidelity_grad_philox_f64_async with F
+ *     replaced by W (rc_lbfgs_advance_f64_async takes the two rows as they are).
+ * Stream conventions (shared_draws), sigma / sigma_rows_dev, NaN rows, empty batches (C = 0 or K = 0: RC_OK, nothing written), the
+ * scratch behind mean_out / moment_out and the sweep-cap counter (rc_stats_grad_general_tiles): as there.  Argument checks before any
+ * HIP call: N, in, out, C, K as there (N > RC_MAX_NSPIN_GRAD: RC_ENOSUP, "N <= 12"); M outside 1 .. RC_MAX_TIMES, weights_dev NULL,
+ * no output: RC_EINVAL; sigma negative or non-finite without sigma_rows_dev: RC_EINVAL.  Enqueue-only: device pointers (the grid
+ * included), launched on `stream`.  Timing against M launches of the single-time entry: DESIGN.md. */
+int rc_mc_fidelity_grad_times_philox_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,
+                                               const double* h0_offdiag, const double* controllers_dev, unsigned long long seed,
+                                               unsigned long long offset, double sigma, const double* sigma_rows_dev,
+                                               int shared_draws, long long C, long long K, int M, const double* tscale_dev,
+                                               const double* tshift_dev, const double* weights_dev, double* wfid_out_dev,
+                                               double* wgrad_out_dev, double* mean_out_dev, double* moment_out_dev);
 
 
 /* Non-Hermitian variant: `diag_imag_dev` [C][K][N] (or NULL) is added to the diagonal as an IMAGINARY part,

@@ -27,7 +27,15 @@ Its last three columns split (b) at alpha = 0.1 into its launches: fidelity, sel
 standalone route on the same table - the floor: it reads each row once.  100 x 10 000 and 1000 x 10 000 at alpha = 0.1 and 0.01,
 11 000 x 100 at alpha = 0.1, 1000 x 100 000 at alpha = 0.01 (a tenth of the launches: its torch sort takes ~0.1 s).
 
-    python scripts/grad_bench.py --select [--out profiles/tail_select_bench.txt]"""
+    python scripts/grad_bench.py --select [--out profiles/tail_select_bench.txt]
+
+--times runs the readout-jitter leg: the gradient on a grid of M readout times, M = 1, 4, 8, 16 (the Gauss-Hermite rule of
+`noise.readout_jitter_nodes(0.1, M)`), N = 5, 7, 10 at 100 x 10 000, sigma = 0.05, same alternation: (a) M launches of
+`mc_fidelity_grad_philox`, mean only, on copies of the controllers with the time entry moved to each grid time (what a
+jitter-averaged gradient took before; the combination of the M rows is not even counted), (b) ONE launch of
+`mc_fidelity_grad_times_philox`, mean only, (c) the same with the moment sums.
+
+    python scripts/grad_bench.py --times [--out profiles/grad_times_bench.txt]"""
 import argparse
 import importlib
 import os
@@ -89,6 +97,65 @@ def philox_leg(args, be, dev, C, K):
                      f"{min(tc) / min(tb):5.2f} | {buf.numel() * 8 / 1e6:8.1f}")
         print(lines[-1], flush=True)
         del buf
+    return "\n".join(lines) + "\n"
+
+
+def times_leg(args, be, dev, C, K):
+    import torch
+    from conftest import highfid_workload
+    noise = importlib.import_module("code-robchar_amd.noise")
+    sigma, seed, sigma_t = 0.05, 7, 0.1
+    lines = [f"# gradient on a grid of M readout times: (a) M launches of mc_fidelity_grad_philox (mean only) against (b) one launch of "
+             f"mc_fidelity_grad_times_philox (mean only) and (c) the same with the moment sums, {C} x {K}, sigma = {sigma}, grid = "
+             f"readout_jitter_nodes({sigma_t}, M), {args.launches} launches after {args.warmup}, routes alternated, {args.repeats} "
+             "repeats (min .. max, us per evaluation), HIP events",
+             f"# device: {torch.cuda.get_device_name(dev)}",
+             "# N  in out   M | (a) M launches us | (b) one launch us | (c) with moments us | (b)/(a) | (c)/(b) (of the minima) | "
+             "(a) - (b) us (of the minima) | 3 x the larger spread us | (a) - (b) > 3 x spread"]
+    work = {w[0]: w for w in (highfid_workload(cid, C=C) for cid in (2, 3, 5))}
+
+    def timed_calls(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize(dev)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(args.launches):
+            fn()
+        e1.record()
+        torch.cuda.synchronize(dev)
+        return e0.elapsed_time(e1) * 1e3 / args.launches
+
+    def spread(v):
+        return f"{min(v):9.1f} .. {max(v):9.1f}"
+
+    for N in (5, 7, 10):
+        _, a, b, ctrl, h0 = work[N]
+        ct = torch.from_numpy(ctrl).to(dev)
+        for M in (1, 4, 8, 16):
+            tshift, weights = noise.readout_jitter_nodes(sigma_t, M)
+            moved = []
+            for j in range(M):
+                cj = ctrl.copy()
+                cj[:, N] = ctrl[:, N] + tshift[j]
+                moved.append(torch.from_numpy(cj).to(dev))
+
+            def single():
+                for cj in moved:
+                    be.mc_fidelity_grad_philox(cj, K, N, a, b, seed, sigma=sigma, h0_diag=h0, want=("mean",))
+
+            def grid(want):
+                be.mc_fidelity_grad_times_philox(ct, K, N, a, b, seed, sigma=sigma, tshift=tshift, weights=weights, h0_diag=h0, want=want)
+
+            ta, tb, tc = [], [], []
+            for _ in range(args.repeats):
+                ta.append(timed_calls(single))
+                tb.append(timed_calls(lambda: grid(("mean",))))
+                tc.append(timed_calls(lambda: grid(("mean", "moment"))))
+            gain, noise_us = min(ta) - min(tb), 3.0 * max(max(ta) - min(ta), max(tb) - min(tb))
+            lines.append(f"{N:3d} {a:3d} {b:3d} {M:3d} | {spread(ta)} | {spread(tb)} | {spread(tc)} | {min(tb) / min(ta):5.2f} | "
+                         f"{min(tc) / min(tb):5.2f} | {gain:9.1f} | {noise_us:9.1f} | {'yes' if gain > noise_us else 'no'}")
+            print(lines[-1], flush=True)
     return "\n".join(lines) + "\n"
 
 
@@ -216,6 +283,7 @@ def main():
     ap.add_argument("--philox", action="store_true", help="the fused-against-two-kernel leg instead of the kernel table")
     ap.add_argument("--listed", action="store_true", help="the CVaR route against the full gradient launch instead of the kernel table")
     ap.add_argument("--select", action="store_true", help="the tail selection against the torch route and the reduction instead of the kernel table")
+    ap.add_argument("--times", action="store_true", help="the gradient on a grid of readout times against M single-time launches instead of the kernel table")
     ap.add_argument("--repeats", type=int, default=3)
     args = ap.parse_args()
     import torch
@@ -223,8 +291,9 @@ def main():
     be = importlib.import_module("code-robchar_amd.backend")
     dev = be.compute_device()
     C, K = 100, 10000
-    if args.philox or args.listed or args.select:
-        text = select_leg(args, be, dev) if args.select else (listed_leg if args.listed else philox_leg)(args, be, dev, C, K)
+    if args.philox or args.listed or args.select or args.times:
+        text = (select_leg(args, be, dev) if args.select else
+                (times_leg if args.times else (listed_leg if args.listed else philox_leg))(args, be, dev, C, K))
         print(text, end="")
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)

@@ -1,0 +1,126 @@
+"""`backend.mc_fidelity_grad_times_philox` - the fidelity gradient on a grid of readout times from one eigen decomposition per
+sample - on the device (the checks of grad_times_checks.py): per-sample outputs BIT FOR BIT against M launches of the existing
+`mc_fidelity_grad_philox` combined on the host; the unit grid; row means and moment sums; the independent reference; W against
+the readout-time kernel; u < 0, u = 0, M = 64, hard inputs; and `optimize_controllers(jitter=...)` end to end.  Shapes are the
+smallest that reach each path: C = 3 rows (one NaN, one with a negative time entry), K = 70 = one tile and a tail of 6 (K = 130
+with shared draws), N = 2, 3 (small), 7 (the residency edge), 9 (the last single pass), 10 (the first multi-pass size), 12 (the
+most passes).  ROBCHAR_GRAD_FORCED_GENERAL=1 announces a -DRC_GRAD_FORCE_GENERAL=1 variant build (scripts/build_variant.sh), in
+which every tile takes the sweep-cap fallback."""
+import importlib
+import os
+
+import numpy as np
+import pytest
+
+import grad_checks as gc
+import grad_times_checks as gt
+
+pytestmark = pytest.mark.gpu
+FORCED = os.environ.get("ROBCHAR_GRAD_FORCED_GENERAL") == "1"      # a -DRC_GRAD_FORCE_GENERAL=1 variant build
+# instantiations whose per-sample outputs miss bit identity with the single-time kernel for a reason the listing explains (none)
+NOT_BIT_IDENTICAL = ()
+
+
+def counted(be, tiles):
+    assert (tiles > 0) if FORCED else (tiles == 0), tiles
+
+
+@pytest.mark.parametrize("N", gt.SIZES)
+def test_per_sample_outputs_are_the_single_time_kernels_bits(be, N):
+    """check 1: per-controller draws (K = 70, even first element) and shared draws (K = 130, odd first element), every pair"""
+    be.grad_general_tiles(reset=True)
+    exact = N not in NOT_BIT_IDENTICAL
+    for (a, b) in gt.pairs(N):
+        gt.check_bits_against_single_time(be, N, a, b, K=70, offset=0, shared=False, exact=exact)
+        gt.check_bits_against_single_time(be, N, a, b, K=130, offset=7, shared=True, exact=exact)
+    counted(be, be.grad_general_tiles(reset=True))
+
+
+@pytest.mark.parametrize("N", (7, 10))
+def test_far_offset_and_per_row_sigma(be, N):
+    """check 1, continued: offset 2^40 + 3, and one sigma per row with a sigma = 0 row"""
+    exact = N not in NOT_BIT_IDENTICAL
+    gt.check_bits_against_single_time(be, N, 0, N - 1, K=70, offset=2 ** 40 + 3, shared=False, exact=exact)
+    gt.check_bits_against_single_time(be, N, 0, N - 1, K=70, offset=2 ** 40 + 3, shared=True, exact=exact)
+    ctrl = gc.philox_ctrl(N, nan_row=None)
+    for shared in (False, True):
+        got = gt.check_bits_against_single_time(be, N, 0, N - 1, K=70, offset=1, shared=shared, sigma=np.array([0.0, 0.02, 0.1]),
+                                                exact=exact, ctrl=ctrl)
+        assert (got["fid"][0] == got["fid"][0, 0]).all() and np.ptp(got["fid"][2]) > 1e-3     # sigma = 0: K identical samples
+
+
+@pytest.mark.parametrize("N", gt.SIZES)
+def test_unit_grid_gives_all_four_outputs_of_the_single_time_kernel(be, N):
+    """check 2"""
+    gt.check_unit_grid(be, N, 0, N - 1, K=70, shared=False)
+    gt.check_unit_grid(be, N, N // 2, N // 2, K=130, shared=True)
+
+
+@pytest.mark.parametrize("N", gt.SIZES)
+def test_row_means_and_moments(be, N):
+    """check 3"""
+    gt.check_means_and_moments(be, N, 0, N - 1, K=70, shared=False)
+    gt.check_means_and_moments(be, N, min(1, N - 1), N // 2, K=130, shared=True)
+
+
+@pytest.mark.parametrize("N", gt.SIZES)
+def test_independent_reference(be, N):
+    """check 4: grad_eigh per grid time, within the bars - the rows with a NaN row and a negative time entry, every pair, both
+    draw modes"""
+    worst = gc.Worst()
+    for (a, b) in gt.pairs(N):
+        gt.check_reference(be, N, a, b, K=70, shared=False, worst=worst, guard=False)
+    gt.check_reference(be, N, 0, N - 1, K=130, shared=True, worst=worst, guard=False)
+    print("gradient on the grid vs eigh:", worst)
+
+
+@pytest.mark.parametrize("N,a,b", [p for p in gt.tc.PAIRS if p[0] <= 12])
+def test_independent_reference_with_teeth(be, N, a, b):
+    """check 4 on the controllers the teeth guards were measured on: a kernel that ignores the grid is off by >= 0.01 in the
+    biases' entries and >= 0.1 in the time entry for half of the samples"""
+    ctrl = gt.guarded_ctrl(N, a, b)
+    gt.check_reference(be, N, a, b, K=70, shared=False, guard=True, ctrl=ctrl)
+    gt.check_reference(be, N, a, b, K=130, shared=True, guard=True, ctrl=ctrl)
+
+
+@pytest.mark.parametrize("N", gt.SIZES)
+def test_w_against_the_readout_time_kernel(be, N):
+    """check 5"""
+    worst = max(gt.check_cross_times_kernel(be, N, a, b) for (a, b) in gt.pairs(N))
+    print(f"N = {N}: max |W - wsum of the times kernel| = {worst:.2e}")
+
+
+@pytest.mark.parametrize("N", (3, 7, 12))
+def test_semantics_and_hard_inputs(be, N):
+    """check 6: every u < 0, u = 0, M = 64; the hard inputs - the product build counts no fallback tile on them"""
+    gt.check_semantics(be, N)
+    be.grad_general_tiles(reset=True)
+    gt.check_hard_inputs(be, N)
+    counted(be, be.grad_general_tiles(reset=True))
+
+
+def test_optimize_controllers_under_jitter(be):
+    """check 8: N = 4, C = 4 rows (one NaN), K = 64 shared draws, max_evals = 20: no finite row ends above its start value, the
+    returned f is 1 - mean of `fidelity_readout_jitter_philox` at the returned x (within the bound of check 5), the NaN row ends
+    with status 5"""
+    import chain_checks as cc
+    noise = importlib.import_module("code-robchar_amd.noise")
+    N, C, K, seed, sigma_t = 4, 4, 64, 31, 0.1
+    nm = noise.structured_perturbation(Nspin=N, inspin=0, outspin=N - 1, noise=0.05)
+    x0 = cc.deloc_ctrl(np.random.default_rng(404), C, N, 0.5)
+    x0[2, 1] = np.nan
+    ok = [0, 1, 3]
+    start = nm.fidelity_jitter_moments_philox(x0, K, seed, sigma_t, shared=True)
+    got = nm.optimize_controllers(x0, K, seed, max_evals=20, jitter=sigma_t)
+    assert got["status"][2] == 5 and (got["status"][ok] != 5).all()
+    f0 = 1.0 - start["fav"]
+    assert (got["f"][ok] <= f0[ok]).all() and (got["f"][ok] < f0[ok]).any(), (got["f"], f0)
+    tshift, weights = noise.readout_jitter_nodes(sigma_t, 8)
+    # (shared draws are row 0's block of the stream: `fidelity_readout_jitter_philox` sees them one row at a time)
+    for c in ok:
+        ws = nm.fidelity_readout_jitter_philox(got["x"][c:c + 1], K, seed, sigma_t)
+        draws = gc.host_draws(seed, 0, (1, K, N, 3), 0.05)
+        # f is 1 - the row mean of W: check 5's bound per sample, averaged over the row like the samples are, plus check 3's
+        # K 2^-52 max|entry| for the order of the row sum (|W| <= sum |w| = 1)
+        bound = float(gt.cross_bound(got["x"][c:c + 1], draws, N, None, tshift, weights).mean()) + K * gt.EPS
+        assert abs(got["f"][c] - (1.0 - ws.mean())) <= bound, (c, got["f"][c], 1.0 - ws.mean(), bound)
