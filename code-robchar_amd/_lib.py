@@ -34,6 +34,7 @@ EXPORTS = (
     "rc_bootstrap_metrics_f64_async", "rc_bootstrap_metrics_f64",
     "rc_mc_fidelity_times_f64_async", "rc_mc_fidelity_times_f64", "rc_mc_fidelity_times_philox_f64_async",
     "rc_stats_times_general_tiles", "rc_mc_fidelity_grad_times_philox_f64_async",
+    "rc_wasserstein_matrix_f64_async", "rc_wasserstein_matrix_f64",
 )
 
 RC_KERNEL_AUTO, RC_KERNEL_TRIDIAG_QL, RC_KERNEL_JACOBI, RC_KERNEL_TRIDIAG_ADJ, RC_KERNEL_EXPM, RC_KERNEL_RING_HH = 0, 1, 2, 3, 4, 5
@@ -184,6 +185,8 @@ def load():
     lib.rc_stats_times_general_tiles.restype = ll
     lib.rc_mc_fidelity_grad_times_philox_f64_async.argtypes = [i, vp, i, i, i, dp, dp, dp, ull, ull, dbl, dp, i, ll, ll, i, dp, dp, dp,
                                                                dp, dp, dp, dp]
+    lib.rc_wasserstein_matrix_f64_async.argtypes = [i, vp, i, dp, ll, dp, ll, ll, dp]
+    lib.rc_wasserstein_matrix_f64.argtypes = [i, i, dp, ll, dp, ll, ll, i, dp]
     _lib = lib
     return lib
 

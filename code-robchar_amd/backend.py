@@ -939,6 +939,83 @@ def bootstrap_metrics(fid, n_boot: int, seed: int, offset: int = 0, q_thresholds
     return res
 
 
+def _sorted_rows_on_device(lib, t):
+    """The rows of the contiguous float64 CUDA tensor `t` (C, K) sorted ascending by the library's row sort, on the current stream."""
+    import torch
+    srt = torch.empty_like(t)
+    C, K = (int(v) for v in t.shape)
+    if C and K:
+        _lib.check(lib.rc_reduce_ex_f64_async(*_on_stream(t.device), _dev_ptr(t), C, K, None, 0, 0.0, None, None, None, None,
+                                              _dev_ptr(srt), 0))
+    return srt
+
+
+def sort_rows(fid, device=None):
+    """The rows of `fid` (C, K) sorted ascending by the library's row sort (what `reduce_metrics(want_sorted=True)["sorted"]` holds,
+    without the metrics): a float64 torch CUDA tensor in, a tensor out, on the current stream; a NumPy array in, an array out."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    if fid.ndim != 2:
+        raise ValueError("fid: expected (C, K)")
+    if _is_torch(fid):
+        fid = fid.contiguous()
+        if not _is_dev_f64(fid):
+            raise ValueError("fid must be a float64 CUDA tensor (or a NumPy array)")
+        return _sorted_rows_on_device(lib, fid)
+    fid = np.ascontiguousarray(fid, dtype=np.float64)
+    srt = np.empty_like(fid)
+    if fid.size:
+        _lib.check(lib.rc_reduce_f64(device_index(device), _ptr(fid), fid.shape[0], fid.shape[1], None, 0, 0.0, None, None, None, None,
+                                     _ptr(srt)))
+    return srt
+
+
+def wasserstein_matrix(a, b=None, p: int = 1, assume_sorted: bool = False, device=None, out=None):
+    """Pairwise p-Wasserstein distances between the rows of `a` (CA, K) and of `b` (CB, K) on the GPU
+    (`rc_wasserstein_matrix_f64_async`; the definition is `wasserstein.matrix_reference`): out[i, j] = (mean_k |a_i(k) - b_j(k)|^p)^(1/p)
+    over the SORTED rows, p = 1 or 2 - for equal-size samples the exact distance between the two empirical distributions.
+    `b=None`: `a` against itself, (CA, CA), bit-for-bit symmetric with a zero diagonal.  A row holding a NaN gives NaN in its whole
+    row and column.  The rows are sorted with the library's row sort unless `assume_sorted` says they already are (what
+    `reduce_metrics(want_sorted=True)["sorted"]` holds).  An element's bits depend on its two rows, K and p alone.
+    Float64 torch CUDA tensors in: a torch tensor on their device (`out`: a preallocated one to fill), enqueued on the current
+    stream, no host synchronisation.  NumPy arrays in: a NumPy array out (the blocking entry on GPU `device`)."""
+    p = int(p)
+    if p not in (1, 2):
+        raise ValueError("p must be 1 or 2")
+    if a.ndim != 2 or (b is not None and (b.ndim != 2 or b.shape[1] != a.shape[1])):
+        raise ValueError("a: expected (CA, K), b: (CB, K) with the same K")
+    if b is not None and _is_torch(a) != _is_torch(b):
+        raise ValueError("a and b: both NumPy arrays or both torch CUDA tensors")
+    CA, K = (int(v) for v in a.shape)
+    CB = int(b.shape[0]) if b is not None else 0
+    shape = (CA, CB if b is not None else CA)
+    lib = _lib.load()
+    _lib.require_gpu()
+    if _is_torch(a):
+        import torch
+        a = a.contiguous()
+        b = None if b is None else b.contiguous()
+        if not _is_dev_f64(a) or (b is not None and not (_is_dev_f64(b) and b.device == a.device)):
+            raise ValueError("a and b must be float64 CUDA tensors on one device (or NumPy arrays)")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=a.device)
+        elif not (_is_dev_f64(out, shape) and out.device == a.device):
+            raise ValueError(f"out: a contiguous float64 CUDA tensor of shape {shape} on the inputs' device")
+        if not assume_sorted:
+            a = _sorted_rows_on_device(lib, a)
+            b = None if b is None else _sorted_rows_on_device(lib, b)
+        _lib.check(lib.rc_wasserstein_matrix_f64_async(*_on_stream(a.device), p, _dev_ptr(a), CA, _dev_ptr(b), CB, K, _dev_ptr(out)))
+        return out
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = None if b is None else np.ascontiguousarray(b, dtype=np.float64)
+    if out is None:
+        out = np.empty(shape, dtype=np.float64)
+    elif not (isinstance(out, np.ndarray) and out.dtype == np.float64 and out.shape == shape and out.flags.c_contiguous):
+        raise ValueError(f"out: a C-contiguous float64 array of shape {shape}")
+    _lib.check(lib.rc_wasserstein_matrix_f64(device_index(device), p, _ptr(a), CA, _ptr(b), CB, K, 1 if assume_sorted else 0, _ptr(out)))
+    return out
+
+
 LBFGS_KINDS = {"raw": 0, "one_minus": 1, "one_minus_plus_std": 2}
 LBFGS_DEFAULTS = {"c1": 1e-4, "gtol": 1e-6, "ftol": 0.0, "maxiter": 100, "maxback": 20}
 

@@ -54,6 +54,7 @@
 #include "sort_core.h"
 #include "select_core.h"
 #include "bootstrap_core.h"
+#include "wasserstein_core.h"
 #include "lbfgs_core.h"
 #include "legacy_rng_core.h"
 #include "mt19937_jump_poly.h"
@@ -114,6 +115,7 @@ using rckp::RingRepairList;
 #include "k_reduce_sort.inc.h"
 #include "k_tail_select.inc.h"
 #include "k_bootstrap.inc.h"
+#include "k_wasserstein.inc.h"
 #include "k_lbfgs.inc.h"
 #include "k_draws.inc.h"
 #include "k_fidelity_philox.inc.h"
@@ -2047,6 +2049,92 @@ int rc_bootstrap_metrics_f64(int device, const double* fid, long long C, long lo
     if (int rc = rc_bootstrap_metrics_f64_async(device, ws.ctx->stream, ws.ptr(s_fid), C, K, B, seed, offset, q_thresholds, nq, rank_lo,
                                                 rank_hi, route, ws.ptr(s_rep), ws.ptr(s_sum)))
         return rc;
+    return ws.stage_out();
+}
+
+// ---- pairwise Wasserstein matrix (ABI 18): tiles of sorted rows against sorted rows (k_wasserstein.inc.h) ------------------------
+static void launch_wasserstein(int P, hipStream_t s, const rcwd::Params& p, bool finish) {
+    const dim3 tiles((unsigned)(p.tiles * p.plan.nparts)), elems((unsigned)((p.CA * p.CB + 255) / 256));
+    if (!finish && P == 1)
+        hipLaunchKernelGGL(wasserstein_tile_kernel<1>, tiles, dim3(rcwd::kThreads), 0, s, p);
+    else if (!finish)
+        hipLaunchKernelGGL(wasserstein_tile_kernel<2>, tiles, dim3(rcwd::kThreads), 0, s, p);
+    else if (P == 1)
+        hipLaunchKernelGGL(wasserstein_finish_kernel<1>, elems, dim3(256), 0, s, p);
+    else
+        hipLaunchKernelGGL(wasserstein_finish_kernel<2>, elems, dim3(256), 0, s, p);
+}
+
+// the checks both entries make before any HIP call; *done: nothing to compute
+static int check_wasserstein(int p, const void* a, long long CA, const void* b, long long* CB, long long K, const void* out, bool* done) {
+    if (!b) *CB = 0;                                                // symmetric mode: CB is ignored
+    if (const char* msg = rcwd::check_args(p, CA, *CB, K)) return fail(RC_EINVAL, msg);
+    *done = CA == 0 || K == 0 || (b && *CB == 0);
+    if (*done) return RC_OK;
+    if (!a || !out) return fail(RC_EINVAL, "NULL array pointer (a, out)");
+    if (const char* msg = rcwd::check_sizes(CA, *CB, K)) return fail(RC_EINVAL, msg);
+    return RC_OK;
+}
+
+int rc_wasserstein_matrix_f64_async(int device, void* stream, int p, const double* a_sorted_dev, long long CA,
+                                    const double* b_sorted_dev, long long CB, long long K, double* out_dev) {
+    bool done = false;
+    if (int rc = check_wasserstein(p, a_sorted_dev, CA, b_sorted_dev, &CB, K, out_dev, &done)) return rc;
+    if (done) return RC_OK;
+    rcwd::Params q{};
+    q.a = a_sorted_dev;
+    q.b = b_sorted_dev ? b_sorted_dev : a_sorted_dev;
+    q.sym = b_sorted_dev ? 0 : 1;
+    q.CA = CA;
+    q.CB = q.sym ? CA : CB;
+    q.K = K;
+    q.nti = (q.CA + rcwd::kTile - 1) / rcwd::kTile;
+    q.ntj = (q.CB + rcwd::kTile - 1) / rcwd::kTile;
+    q.tiles = q.sym ? q.nti * (q.nti + 1) / 2 : q.nti * q.ntj;
+    q.plan = rcwd::choose_plan(q.tiles, K);
+    q.out = out_dev;
+    if (q.tiles > 0x7fffffffLL / q.plan.nparts) return fail(RC_EINVAL, "too many workgroups for one launch");
+    RC_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    // partial sums of THIS call, allocated and released in stream order
+    StreamFree part_ws{nullptr, s};
+    if (q.plan.nparts > 1) {
+        RC_HIP_CHECK(hipMallocAsync(&part_ws.p, (size_t)q.plan.nparts * q.CA * q.CB * sizeof(double), s));
+        q.part = (double*)part_ws.p;
+    }
+    launch_wasserstein(p, s, q, false);
+    RC_HIP_CHECK(hipGetLastError());
+    if (q.plan.nparts > 1) {
+        launch_wasserstein(p, s, q, true);
+        RC_HIP_CHECK(hipGetLastError());
+    }
+    return RC_OK;
+}
+
+int rc_wasserstein_matrix_f64(int device, int p, const double* a, long long CA, const double* b, long long CB, long long K,
+                              int presorted, double* out) {
+    bool done = false;
+    if (int rc = check_wasserstein(p, a, CA, b, &CB, K, out, &done)) return rc;
+    if (done) return RC_OK;
+    if (int rc = device_in_range(device)) return rc;
+    std::lock_guard<std::mutex> lk(g_ctx[device].mu);
+    Staging ws;
+    if (int rc = get_ctx(device, &ws.ctx)) return rc;
+    const size_t nb_a = (size_t)CA * K * sizeof(double), nb_b = (size_t)CB * K * sizeof(double);
+    const int s_a = ws.in(a, nb_a), s_b = b ? ws.in(b, nb_b) : -1, s_out = ws.out(out, (size_t)CA * (b ? CB : CA) * sizeof(double)),
+              s_as = presorted ? -1 : ws.plan.scratch(nb_a), s_bs = (presorted || !b) ? -1 : ws.plan.scratch(nb_b);
+    if (int rc = ws.stage_in()) return rc;
+    const double *da = ws.ptr(s_a), *db = b ? ws.ptr(s_b) : nullptr;
+    if (!presorted) {                                               // the row sort of the reduce entry
+        if (int rc = enqueue_reduce(ws.ctx->stream, da, CA, K, nullptr, 0, 0.0, nullptr, nullptr, nullptr, nullptr, ws.ptr(s_as))) return rc;
+        da = ws.ptr(s_as);
+        if (b) {
+            if (int rc = enqueue_reduce(ws.ctx->stream, db, CB, K, nullptr, 0, 0.0, nullptr, nullptr, nullptr, nullptr, ws.ptr(s_bs)))
+                return rc;
+            db = ws.ptr(s_bs);
+        }
+    }
+    if (int rc = rc_wasserstein_matrix_f64_async(device, ws.ctx->stream, p, da, CA, db, CB, K, ws.ptr(s_out))) return rc;
     return ws.stage_out();
 }
 

@@ -922,6 +922,85 @@ class MCDataSim:
         named = rim_metrics.bootstrap_named(res["summary"].cpu().numpy())
         return {metric: {k: v.reshape(L, C).tolist() for k, v in tab.items()} for metric, tab in named.items()}
 
+    # ------------------------------------------------------------------ pairwise Wasserstein distances between controllers
+    def get_wasserstein_dict(self, training_noise: str = None, noises: np.ndarray = None, algoname=None, p: int = 1) -> dict:
+        """Pairwise p-Wasserstein distances (p = 1 or 2) between the fidelity distributions of an algorithm's controllers, per sigma
+        level:
+
+            {algo: ndarray [L][C][C]}      W[j, c, d] = W_p between the K fidelities of controllers c and d at level j
+
+        (symmetric, zero diagonal; `wasserstein.matrix_reference` is the definition).  It compares two controllers' robustness
+        profiles with each other where RIM_p compares one with the ideal distribution - the input of a clustering or an embedding
+        of the controllers.  Controllers padded up to `numcontrollers` give NaN rows and columns.
+
+        The fidelities are those of `get_fid_dists` (computed there if no cache file has them): the `DeviceFids` handle where the
+        tensor is on the GPU, the host table otherwise.  Per algorithm ONE row sort over the L * C rows, then one launch per level
+        (`backend.sort_rows`, `backend.wasserstein_matrix`).
+
+        Cached in NumPy's `.npz` format in `get_mcname(...) + "w"` together with `p`; the file is reused only when `p` and the
+        shape (L, C, C) match (and not written with cache_format="none").  One GPU: raises NotImplementedError under an initialised
+        process group or with `devices=...`."""
+        if self.devices is not None:
+            raise NotImplementedError("get_wasserstein_dict runs on one GPU (devices=... is not supported)")
+        try:
+            import torch.distributed as dist
+            grouped = dist.is_available() and dist.is_initialized()
+        except ImportError:
+            grouped = False
+        if grouped:
+            raise NotImplementedError("get_wasserstein_dict runs on one GPU (not under an initialised process group)")
+        p = int(p)
+        if p not in (1, 2):
+            raise ValueError("p must be 1 or 2")
+        if isinstance(algoname, str):
+            algos = [algoname]
+        elif algoname is None:
+            algos = list(self.algos)
+        else:
+            algos = list(algoname)
+        if noises is None:
+            noises = self.noises
+        if training_noise is None:
+            training_noise = self.training_noise
+        noises = np.asarray(noises)
+        shape = (int(noises.size), self.numcontrollers, self.numcontrollers)
+        path = self.get_mcname(training_noise, noises) + "w"
+        table = {}
+        if os.path.exists(path):
+            with np.load(path) as cached:
+                if "p" in cached.files and int(cached["p"]) == p:
+                    table = {k[5:]: cached[k] for k in cached.files if k.startswith("algo:") and cached[k].shape == shape}
+        missing = [a for a in algos if a not in table]
+        if missing:
+            dists = self.get_fid_dists(training_noise, noises, algoname if isinstance(algoname, str) else None)
+            for name in missing:
+                table[name] = self._wasserstein_of_algo(dists[name], p)
+            if self.cache_format != "none":
+                with open(path, "wb") as fh:
+                    np.savez(fh, p=np.int64(p), **{"algo:" + name: arr for name, arr in table.items()})
+        return {name: table[name] for name in algos}
+
+    def _wasserstein_of_algo(self, dists, p: int) -> np.ndarray:
+        """One algorithm of `get_wasserstein_dict`: the (L, C, K) tensor sorted as L * C rows, then level by level."""
+        if isinstance(dists, DeviceFids) and dists.tensor is not None:
+            import torch
+            L, C, K = dists.shape
+            rows = dists.tensor
+            if int(rows.shape[1]) < C:                   # the padded controllers: NaN rows
+                full = torch.full((L, C, K), float("nan"), dtype=torch.float64, device=rows.device)
+                full[:, :int(rows.shape[1])] = rows
+                rows = full
+        else:
+            rows = np.ascontiguousarray(np.asarray(dists, dtype=np.float64))
+            L, C, K = rows.shape
+        out = np.full((L, C, C), np.nan)
+        if L and C and K:
+            srt = backend.sort_rows(rows.reshape(L * C, K))
+            for j in range(L):
+                w = backend.wasserstein_matrix(srt[j * C:(j + 1) * C], None, p=p, assume_sorted=True)
+                out[j] = w.cpu().numpy() if backend._is_torch(w) else np.asarray(w)
+        return out
+
     # ------------------------------------------------------------------ second caller of the kernel
     _RIMS_CHUNK_DRAWS = 1 << 27          # host draws per batch (1 GiB of fp64)
 

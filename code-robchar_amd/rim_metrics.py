@@ -202,6 +202,15 @@ def bootstrap_metrics(fids, n_boot: int = 1000, seed: int = 0, conf: float = 0.9
     return named
 
 
+def wasserstein_matrix(a, b=None, p: int = 1, assume_sorted: bool = False, device=None):
+    """Pairwise p-Wasserstein distances (p = 1, 2) between the fidelity samples in the rows of `a` (CA, K) and `b` (CB, K; None: `a`
+    against itself), computed on the GPU (`backend.wasserstein_matrix`): (CA, CB) array, out[i, j] = W_p between the empirical
+    distributions of row i and row j.  Against a row of ones it is RIM_p (`wd_from_ideal_fids` for p = 1)."""
+    arr = np.ascontiguousarray(_as_fids(a).reshape(-1, np.shape(a)[-1]), dtype=np.float64)
+    other = None if b is None else np.ascontiguousarray(_as_fids(b).reshape(-1, np.shape(b)[-1]), dtype=np.float64)
+    return backend.wasserstein_matrix(arr, other, p=p, assume_sorted=assume_sorted, device=device)
+
+
 @dataclass
 class Q_partial:
     """mcsim.py:169-176: Q_fids with the threshold bound at construction."""

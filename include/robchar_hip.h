@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 17     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 18     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -74,7 +74,8 @@ extern "C" {
                                   15: + rc_bootstrap_metrics_f64_async, rc_bootstrap_metrics_f64 (additive);
                                   16: + rc_mc_fidelity_times_f64_async, rc_mc_fidelity_times_f64,
                                       rc_mc_fidelity_times_philox_f64_async, rc_stats_times_general_tiles, RC_MAX_TIMES (additive);
-                                  17: + rc_mc_fidelity_grad_times_philox_f64_async (additive) */
+                                  17: + rc_mc_fidelity_grad_times_philox_f64_async (additive);
+                                  18: + rc_wasserstein_matrix_f64_async, rc_wasserstein_matrix_f64 (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -453,6 +454,33 @@ int rc_bootstrap_metrics_f64_async(int device, void* stream, const double* fid_d
 int rc_bootstrap_metrics_f64(int device, const double* fid, long long C, long long K, long long B, unsigned long long seed,
                              unsigned long long offset, const double* q_thresholds, int nq, long long rank_lo, long long rank_hi,
                              int route, double* rep_out, double* summary_out);
+
+/* (ABI 18) Pairwise Wasserstein distances between fidelity rows: for rows a, b of equal length K, each sorted ascending,
+ *     W_1 = (1/K) sum_k |a_(k) - b_(k)|,      W_2 = sqrt((1/K) sum_k (a_(k) - b_(k))^2),
+ * the exact p-Wasserstein distance between the two empirical distributions (a row of ones as b gives RIM_p).  p = 1 or 2.
+ * The definition is code-robchar_amd/wasserstein.py (NumPy, math.fsum).
+ *     a [CA][K], b [CB][K]   row-major, every row sorted ascending (what rc_reduce_f64's sorted_out holds)
+ *     out [CA][CB]           out[i][j] = W_p(a_i, b_j)
+ * b = NULL: the matrix of a against itself, out [CA][CA]; CB is then ignored, whatever it holds.  Only tiles on or above the
+ * diagonal are computed and each is written to both places: out equals its transpose bit for bit, and the diagonal of a NaN-free
+ * row is exactly 0.
+ * Arithmetic: d = a - b, then acc + |d| (p = 1) or fma(d, d, acc) (p = 2) - never sum a^2 + sum b^2 - 2 sum a b, which cancels for
+ * close rows; one IEEE division by K, the correctly rounded square root.  A row holding any NaN gives NaN in its whole row and
+ * column by ordinary propagation (no min / max anywhere).  The K terms are summed in a fixed order that depends on K alone (in
+ * order inside chunks of 256, the chunk sums in order inside blocks of 1024, those inside blocks of 4096, those in order), so an
+ * element's bits depend on its two rows, K and p only: not on CA, CB, the position of the rows, the mode, or how the launch
+ * spreads K over workgroups.  No atomics: when K is split, the partial sums go to a scratch buffer allocated and released in stream
+ * order and a finishing launch adds them in that order.
+ * Argument checks before any HIP call, RC_EINVAL with a message: p outside {1, 2}; CA, K or (with b given) CB negative.  Then CA,
+ * K or (with b given) CB equal to 0: RC_OK, nothing written.  Then a or out NULL: RC_EINVAL; more than 2^31 - 1 rows: RC_EINVAL.
+ * _async: enqueue-only on `stream`, device pointers, sorted rows are a precondition; no synchronisation.  The blocking entry
+ * takes host or device arrays; with presorted = 0 it sorts the rows first (the row sort of rc_reduce_f64), leaving a and b as
+ * they are.  Timing: DESIGN.md. */
+int rc_wasserstein_matrix_f64_async(int device, void* stream, int p, const double* a_sorted_dev, long long CA,
+                                    const double* b_sorted_dev /* NULL: B = A, symmetric */, long long CB, long long K,
+                                    double* out_dev /* [CA][CB], or [CA][CA] */);
+int rc_wasserstein_matrix_f64(int device, int p, const double* a, long long CA, const double* b, long long CB, long long K,
+                              int presorted, double* out);
 
 /* (ABI 6) 1 when the kernel above is the faster of the two bit-identical routes for this geometry (N <= 13, or N = 14 with
  * {in, out} = {0, N-1}), else 0; 0 everywhere when ROBCHAR_PHILOX_FUSED=0 is in the environment (read per call).  The ONE
