@@ -35,6 +35,7 @@ EXPORTS = (
     "rc_mc_fidelity_times_f64_async", "rc_mc_fidelity_times_f64", "rc_mc_fidelity_times_philox_f64_async",
     "rc_stats_times_general_tiles", "rc_mc_fidelity_grad_times_philox_f64_async",
     "rc_wasserstein_matrix_f64_async", "rc_wasserstein_matrix_f64",
+    "rc_sobol_dirnum_u32", "rc_draws_sobol_f64_async", "rc_draws_sobol_f64", "rc_mc_fidelity_sobol_f64_async",
 )
 
 RC_KERNEL_AUTO, RC_KERNEL_TRIDIAG_QL, RC_KERNEL_JACOBI, RC_KERNEL_TRIDIAG_ADJ, RC_KERNEL_EXPM, RC_KERNEL_RING_HH = 0, 1, 2, 3, 4, 5
@@ -187,6 +188,10 @@ def load():
                                                                dp, dp, dp, dp]
     lib.rc_wasserstein_matrix_f64_async.argtypes = [i, vp, i, dp, ll, dp, ll, ll, dp]
     lib.rc_wasserstein_matrix_f64.argtypes = [i, i, dp, ll, dp, ll, ll, i, dp]
+    lib.rc_sobol_dirnum_u32.argtypes = [i, dp]
+    lib.rc_draws_sobol_f64_async.argtypes = [i, vp, i, dp, dp, ll, i, ll, ll, dbl, dp, ll, ll, dp, dp]
+    lib.rc_draws_sobol_f64.argtypes = [i, i, dp, dp, ll, i, ll, ll, dbl, dp, ll, ll, dp, dp]
+    lib.rc_mc_fidelity_sobol_f64_async.argtypes = [i, vp, i, i, i, i, dp, dp, dp, dp, dp, ll, i, ll, ll, dbl, dp, ll, ll, dp]
     _lib = lib
     return lib
 

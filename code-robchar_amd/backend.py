@@ -1393,3 +1393,122 @@ def mc_metrics_gathered(comm: "RcclComm", controllers, n_draws: int, nspin: int,
     if want_fid:
         res["fid"] = fid
     return res
+
+
+# ---- randomised quasi-Monte Carlo: scrambled Sobol points (the definition: sobol.py) --------------------------------------------
+MAX_NSPIN_SOBOL = 13                 # RC_MAX_NSPIN_SOBOL of include/robchar_hip.h
+
+
+def _sobol_tables(dirnum, shift, P, K, skip, C, D=None):
+    """The Sobol arguments validated BEFORE the library is loaded -> (dirnum, shift, C, R, D, shift_cstride): dirnum (R, D, 32) (or
+    (D, 32): one replicate), shift (Cs, R, D) with Cs = 1 (row 0 for every controller row, stride 0) or Cs = C (stride R D); the
+    words as NumPy uint32 arrays or torch CUDA tensors of a 32-bit integer type (uint32 / int32: the bit patterns)."""
+    from . import sobol
+    if not _is_torch(dirnum):
+        dirnum = np.ascontiguousarray(dirnum, dtype=np.uint32)
+    if not _is_torch(shift):
+        shift = np.ascontiguousarray(shift, dtype=np.uint32)
+    if dirnum.ndim == 2:
+        dirnum = dirnum[None]
+    if dirnum.ndim != 3 or dirnum.shape[2] != 32:
+        raise ValueError(f"dirnum: expected (R, D, 32), got {tuple(dirnum.shape)}")
+    R, Dn = int(dirnum.shape[0]), int(dirnum.shape[1])
+    if D is not None and Dn != D:
+        raise ValueError(f"dirnum: expected {D} dimensions, got {Dn}")
+    if shift.ndim == 2:
+        shift = shift[None]
+    if shift.ndim != 3 or tuple(shift.shape[1:]) != (R, Dn):
+        raise ValueError(f"shift: expected (1 or C, {R}, {Dn}), got {tuple(shift.shape)}")
+    Cs = int(shift.shape[0])
+    C = Cs if C is None else int(C)
+    if C < 0 or Cs not in (1, C):
+        raise ValueError(f"shift: expected 1 or {C} rows, got {Cs}")
+    sobol.check_contract(Dn, R, P, skip, K)
+    return dirnum, shift, C, R, Dn, (R * Dn if (Cs == C and C > 1) else 0)
+
+
+def _u32_on(t, dev):
+    """Sobol words as a contiguous 32-bit integer tensor on `dev` (a NumPy uint32 array is uploaded)."""
+    import torch
+    if not _is_torch(t):
+        return torch.from_numpy(t.view(np.int32)).to(dev)
+    if t.element_size() != 4 or t.is_floating_point() or not t.is_cuda or not t.is_contiguous():
+        raise ValueError("Sobol tables: contiguous CUDA tensors of a 32-bit integer type")
+    return t
+
+
+def _sobol_generate(want, dirnum, shift, P, K, skip, sigma, C, device, as_torch):
+    dirnum, shift, C, R, D, stride = _sobol_tables(dirnum, shift, P, K, skip, C)
+    K, P, skip = int(K), int(P), int(skip)
+    per_row = not isinstance(sigma, (int, float)) and np.ndim(sigma) > 0
+    if per_row and not _is_torch(sigma):
+        sigma = np.ascontiguousarray(sigma, dtype=np.float64)
+    if per_row and tuple(sigma.shape) != (C,):
+        raise ValueError("sigma: a float or a (C,) tensor")
+    lib = _lib.load()
+    _lib.require_gpu()
+    on_device = as_torch or _is_torch(dirnum) or _is_torch(shift)
+    if on_device:
+        import torch
+        dev = next((t.device for t in (dirnum, shift) if _is_torch(t)), None)
+        if dev is None:
+            dev = device if hasattr(device, "type") else torch.device("cuda", device_index(device))
+        dn, sh = _u32_on(dirnum, dev), _u32_on(shift, dev)
+        rows = None
+        if per_row:
+            rows = (sigma if _is_torch(sigma) else torch.from_numpy(np.ascontiguousarray(sigma, dtype=np.float64))).to(
+                device=dev, dtype=torch.float64).contiguous()
+        res, out_ptr = _outputs(("draws", "bits"), want, {"draws": (C, K, D), "bits": (C, K, D)}, dev, {"bits": torch.int32})
+        _lib.check(lib.rc_draws_sobol_f64_async(*_on_stream(dev), D, _dev_ptr(dn), _dev_ptr(sh), stride, R, P, skip,
+                                                0.0 if per_row else float(sigma), _dev_ptr(rows), C, K, *out_ptr))
+        return res
+    rows = np.ascontiguousarray(sigma, dtype=np.float64) if per_row else None
+    res = {k: np.empty((C, K, D), dtype=np.float64 if k == "draws" else np.uint32) for k in want}
+    _lib.check(lib.rc_draws_sobol_f64(device_index(device), D, _ptr(dirnum), _ptr(shift), stride, R, P, skip,
+                                      0.0 if per_row else float(sigma), _ptr(rows), C, K, _ptr(res.get("draws")), _ptr(res.get("bits"))))
+    return res
+
+
+def sobol_points(dirnum, shift, P: int, K: int, skip: int = 0, C=None, device=None, as_torch: bool = False):
+    """The scrambled Sobol points of `sobol.points(dirnum, shift, P, K, skip, C)` made on the GPU (`rc_draws_sobol_f64[_async]`),
+    bit for bit: (C, K, D) words.  NumPy tables in -> NumPy uint32 out (blocking); torch CUDA tables, or `as_torch` -> an int32
+    torch tensor holding the words' bit patterns, enqueued on the current stream."""
+    return _sobol_generate(("bits",), dirnum, shift, P, K, skip, 1.0, C, device, as_torch)["bits"]
+
+
+def sobol_normal(dirnum, shift, P: int, K: int, skip: int = 0, sigma=1.0, C=None, device=None, as_torch: bool = False):
+    """sigma-scaled normals of the scrambled Sobol points (`sobol.normals`, to a few ulp): (C, K, D) float64 - for D = 3 N,
+    reshaped to (C, K, N, 3), the draw tensor every entry that reads draws takes.  Sample k of row c is point skip + (k mod P) of
+    replicate k // P.  `sigma`: a float, or a (C,) array / tensor (one scale per controller row).  NumPy / torch as `sobol_points`."""
+    return _sobol_generate(("draws",), dirnum, shift, P, K, skip, sigma, C, device, as_torch)["draws"]
+
+
+def sobol_fused_supported(nspin: int, ring: bool = False, kernel: str = "auto") -> bool:
+    """Can `mc_fidelity_sobol` take this geometry (chain, N <= 13, eigenvalue-only kernels)?"""
+    return (not ring) and 2 <= nspin <= MAX_NSPIN_SOBOL and kernel in ("auto", "tridiag_adj")
+
+
+def mc_fidelity_sobol(controllers, n_draws: int, nspin: int, inspin: int, outspin: int, dirnum, shift, P: int, skip: int = 0,
+                      sigma=0.05, h0_diag=None, h0_offdiag=None, kernel: str = "auto", out=None):
+    """Fidelities with the scrambled Sobol normals generated INSIDE the kernel (`rc_mc_fidelity_sobol_f64_async`): controllers
+    (C, N+1) torch CUDA tensor (a NumPy array is uploaded to the current device) -> (C, K) torch tensor on that device, enqueued on
+    the current stream; bit-identical to `mc_fidelity(controllers, sobol_normal(dirnum, shift, P, K, skip, sigma, C).view(C, K, N, 3))`
+    without that tensor.  dirnum (R, 3 N, 32), shift (1 or C, R, 3 N): `sobol.scramble`; `sigma`: a float, or a (C,) tensor / array.
+    Chain topology, N <= 13, kernel "auto" / "tridiag_adj"."""
+    import torch
+    _check_geometry(nspin, inspin, outspin)
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
+    nrows = int(controllers.shape[0]) if hasattr(controllers, "shape") else len(controllers)
+    dirnum, shift, C, R, D, stride = _sobol_tables(dirnum, shift, P, n_draws, skip, nrows, D=3 * nspin)
+    ctrl, rows, C, K, draw_args = _generated_draws_args(controllers, n_draws, sigma, 0, 0, nspin)
+    lib = _lib.load()
+    dev = ctrl.device
+    dn, sh = _u32_on(dirnum, dev), _u32_on(shift, dev)
+    if out is None:
+        out = torch.empty((C, K), dtype=torch.float64, device=dev)
+    elif not _is_dev_f64(out, (C, K)):
+        raise ValueError("out must be a contiguous float64 CUDA tensor of shape (C, K)")
+    _lib.check(lib.rc_mc_fidelity_sobol_f64_async(*_on_stream(dev), _lib.KERNELS[kernel], nspin, inspin, outspin, _ptr(h0d), _ptr(h0o),
+                                                  _dev_ptr(ctrl), _dev_ptr(dn), _dev_ptr(sh), stride, R, int(P), int(skip),
+                                                  draw_args[2], draw_args[3], C, K, _dev_ptr(out)))
+    return out

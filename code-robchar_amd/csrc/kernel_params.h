@@ -185,4 +185,17 @@ struct TimesParams {
     StaticH h0;
 };
 
+// scrambled Sobol points (sobol_core.h; the definition: code-robchar_amd/sobol.py): sample k of controller row c is point
+// skip + (k mod P) of replicate k / P; its D coordinates read dirnum[r][d][0..31] and shift[c or 0][r][d]
+struct SobolDraws {
+    const unsigned int* dirnum;       // [R][D][32]
+    const unsigned int* shift;        // [Cs][R][D]
+    long long shift_cstride;          // R D (a row per controller) or 0 (row 0 for all)
+    long long P;                      // points per replicate
+    unsigned long long skip;          // first point of every replicate
+    const double* sigma_rows;         // [C] scale per controller row, or NULL: `sigma` for all
+    double sigma;
+    int R, D;
+};
+
 }  // namespace rckp

@@ -59,6 +59,7 @@
 #include "legacy_rng_core.h"
 #include "mt19937_jump_poly.h"
 #include "ws_plan.h"
+#include "sobol_joe_kuo_96.h"
 
 // The largest instantiations live in a second translation unit (robchar_large.hip) that compiles in parallel with this one:
 // chains of 17 .. 24 spins (general adjugate mode), rings of 11 .. 16 spins (mixed route + repair, all-fp64 route).  Each
@@ -83,6 +84,12 @@ __attribute__((visibility("hidden"))) int rc_sens_philox_launch(int N, void* str
 __attribute__((visibility("hidden"))) int rc_times_launch(int N, void* stream, const rckp::TimesParams* p);
 __attribute__((visibility("hidden"))) int rc_times_philox_launch(int N, void* stream, const rckp::TimesParams* p);
 __attribute__((visibility("hidden"))) int rc_times_counter_addr(void** addr);
+// fifth translation unit (robchar_qmc.hip): the scrambled Sobol generator and the fidelity kernel that generates its Sobol normals
+__attribute__((visibility("hidden"))) int rc_qmc_draws_launch(void* stream, const rckp::SobolDraws* q, long long C, long long K,
+                                                              double* draws, unsigned int* bits);
+__attribute__((visibility("hidden"))) int rc_qmc_fidelity_launch(int N, int ends, void* stream, const rckp::FidParams* p,
+                                                                 const rckp::SobolDraws* q);
+__attribute__((visibility("hidden"))) int rc_qmc_counter_addr(int which, void** addr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1368,7 +1375,8 @@ void run_gather_share_locked(GatherJob* j) {
 // ------------------------------------------------------------------------------------------------
 // Sum of a diagnostic tile counter (synchronises the device; optionally zeroes it): `slots` unsigned 64-bit counters at each of
 // the n device addresses addr_of[u]() gives (a hipError_t).  `what`: the text of any failure; NULL: a counter of the chain /
-// ring kernels - this unit's copy, then the second unit's (robchar_large.hip: chains of 17 .. 24 spins, rings of 11 .. 16) -,
+// ring kernels - this unit's copy, then the second unit's (robchar_large.hip: chains of 17 .. 24 spins, rings of 11 .. 16) and
+// the Sobol fidelity kernel's (robchar_qmc.hip) -,
 // whose texts say what failed and in which unit.
 typedef int (*CounterAddr)(void**);
 static long long read_tile_counter(int device, int reset, const CounterAddr* addr_of, int n, int slots, const char* what) {
@@ -1379,7 +1387,7 @@ static long long read_tile_counter(int device, int reset, const CounterAddr* add
     const size_t nb = sizeof(unsigned long long) * slots;
     unsigned long long sum = 0;
     for (int u = 0; u < n; ++u) {
-        const std::string unit = u ? " the tile counter (second unit) failed" : " the tile counter failed";
+        const std::string unit = u == 0 ? " the tile counter failed" : u == 1 ? " the tile counter (second unit) failed" : " the tile counter (Sobol unit) failed";
         unsigned long long v[64] = {0};
         void* addr = nullptr;
         if ((u == 0 && hipDeviceSynchronize() != hipSuccess) || addr_of[u](&addr) != hipSuccess || !addr ||
@@ -1571,14 +1579,16 @@ int rc_device_count(void) {
 const char* rc_last_error(void) { return g_last_error.c_str(); }
 
 long long rc_stats_general_tiles(int device, int reset) {
-    const CounterAddr units[2] = {[](void** a) { return (int)hipGetSymbolAddress(a, HIP_SYMBOL(g_general_tiles)); },
-                                  [](void** a) { return rc_large_counter_addr(0, a); }};
-    return read_tile_counter(device, reset, units, 2, 1, nullptr);
+    const CounterAddr units[3] = {[](void** a) { return (int)hipGetSymbolAddress(a, HIP_SYMBOL(g_general_tiles)); },
+                                  [](void** a) { return rc_large_counter_addr(0, a); },
+                                  [](void** a) { return rc_qmc_counter_addr(0, a); }};
+    return read_tile_counter(device, reset, units, 3, 1, nullptr);
 }
 long long rc_stats_polish_tiles(int device, int reset) {
-    const CounterAddr units[2] = {[](void** a) { return (int)hipGetSymbolAddress(a, HIP_SYMBOL(g_polish_tiles)); },
-                                  [](void** a) { return rc_large_counter_addr(1, a); }};
-    return read_tile_counter(device, reset, units, 2, 64, nullptr);
+    const CounterAddr units[3] = {[](void** a) { return (int)hipGetSymbolAddress(a, HIP_SYMBOL(g_polish_tiles)); },
+                                  [](void** a) { return rc_large_counter_addr(1, a); },
+                                  [](void** a) { return rc_qmc_counter_addr(1, a); }};
+    return read_tile_counter(device, reset, units, 3, 64, nullptr);
 }
 
 int rc_set_fidelity_kernel(int kernel) {
@@ -2310,6 +2320,106 @@ int rc_mc_fidelity_philox_f64_async(int device, void* stream, int kernel, int N,
 #undef RC_CASE
     }
     return fail(RC_EINVAL, "unsupported N");
+}
+
+// ---- randomised quasi-Monte Carlo (ABI 19): scrambled Sobol points, code-robchar_amd/sobol.py is the definition -----------------
+int rc_sobol_dirnum_u32(int D, unsigned int* out_host) {
+    if (D < 1 || D > RC_SOBOL_MAX_DIM) return fail(RC_EINVAL, "D must be in [1, 96]");
+    if (!out_host) return fail(RC_EINVAL, "NULL output pointer");
+    memcpy(out_host, kSobolJoeKuo96, (size_t)D * 32 * sizeof(unsigned int));
+    return RC_OK;
+}
+
+// the contract of sobol.py, in its order; fills `q`
+static int check_sobol(int D, const unsigned int* dirnum, const unsigned int* shift, long long shift_cstride, int R, long long P,
+                       long long skip, double sigma, const double* sigma_rows, long long C, long long K, rckp::SobolDraws* q) {
+    if (D < 1 || D > RC_SOBOL_MAX_DIM) return fail(RC_EINVAL, "D must be in [1, 96]");
+    if (C < 0 || K < 0) return fail(RC_EINVAL, "C and K must be non-negative");
+    if (R < 1 || P < 1) return fail(RC_EINVAL, "R and P must be positive");
+    if (P > (1LL << 32)) return fail(RC_EINVAL, "P must not exceed 2^32");
+    if (K > (long long)R * P) return fail(RC_EINVAL, "K must not exceed R P");
+    if (skip < 0 || skip % 64 != 0) return fail(RC_EINVAL, "skip must be a non-negative multiple of 64");
+    if (R > 1 && P % 64 != 0) return fail(RC_EINVAL, "P must be a multiple of 64 when R > 1");
+    if (skip + (P < K ? P : K) > (1LL << 32)) return fail(RC_EINVAL, "skip + min(P, K) must not exceed 2^32");
+    if (shift_cstride != 0 && shift_cstride != (long long)R * D) return fail(RC_EINVAL, "shift_cstride must be 0 or R D");
+    *q = rckp::SobolDraws{dirnum, shift, shift_cstride, P, (unsigned long long)skip, sigma_rows, sigma, R, D};
+    return RC_OK;
+}
+
+int rc_draws_sobol_f64_async(int device, void* stream, int D, const unsigned int* dirnum_dev, const unsigned int* shift_dev,
+                             long long shift_cstride, int R, long long P, long long skip, double sigma, const double* sigma_rows_dev,
+                             long long C, long long K, double* draws_out_dev, unsigned int* bits_out_dev) {
+    rckp::SobolDraws q;
+    if (int rc = check_sobol(D, dirnum_dev, shift_dev, shift_cstride, R, P, skip, sigma, sigma_rows_dev, C, K, &q)) return rc;
+    if (!draws_out_dev && !bits_out_dev) return fail(RC_EINVAL, "no output requested (draws_out and bits_out are both NULL)");
+    if (C == 0 || K == 0) return RC_OK;
+    if (!dirnum_dev || !shift_dev) return fail(RC_EINVAL, "NULL array pointer");
+    if (C * ((K + 63) / 64) > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    RC_HIP_CHECK(hipSetDevice(device));
+    const hipError_t e = (hipError_t)rc_qmc_draws_launch(stream, &q, C, K, draws_out_dev, bits_out_dev);
+    if (e != hipSuccess) return fail(RC_EHIP, std::string("rc_qmc_draws_launch: ") + hipGetErrorString(e));
+    return RC_OK;
+}
+
+int rc_draws_sobol_f64(int device, int D, const unsigned int* dirnum, const unsigned int* shift, long long shift_cstride, int R,
+                       long long P, long long skip, double sigma, const double* sigma_rows, long long C, long long K,
+                       double* draws_out, unsigned int* bits_out) {
+    rckp::SobolDraws q;
+    if (int rc = check_sobol(D, dirnum, shift, shift_cstride, R, P, skip, sigma, sigma_rows, C, K, &q)) return rc;
+    if (!draws_out && !bits_out) return fail(RC_EINVAL, "no output requested (draws_out and bits_out are both NULL)");
+    if (C == 0 || K == 0) return RC_OK;
+    if (!dirnum || !shift) return fail(RC_EINVAL, "NULL array pointer");
+    if (int rc = device_in_range(device)) return rc;
+    std::lock_guard<std::mutex> lk(g_ctx[device].mu);
+    Staging ws;
+    if (int rc = get_ctx(device, &ws.ctx)) return rc;
+    const size_t n = (size_t)C * K * D;
+    const int s_dir = ws.in(dirnum, (size_t)R * D * 32 * sizeof(unsigned int)),
+              s_shift = ws.in(shift, (size_t)(shift_cstride ? C : 1) * R * D * sizeof(unsigned int)),
+              s_rows = sigma_rows ? ws.in(sigma_rows, (size_t)C * sizeof(double)) : -1,
+              s_draws = ws.out(draws_out, n * sizeof(double)), s_bits = ws.out(bits_out, n * sizeof(unsigned int));
+    if (int rc = ws.stage_in()) return rc;
+    if (int rc = rc_draws_sobol_f64_async(device, ws.ctx->stream, D, (const unsigned int*)ws.ptr(s_dir), (const unsigned int*)ws.ptr(s_shift),
+                                          shift_cstride, R, P, skip, sigma, s_rows >= 0 ? ws.ptr(s_rows) : nullptr, C, K,
+                                          ws.ptr(s_draws), (unsigned int*)ws.ptr(s_bits)))
+        return rc;
+    return ws.stage_out();
+}
+
+int rc_mc_fidelity_sobol_f64_async(int device, void* stream, int kernel, int N, int in, int out, const double* h0_diag,
+                                   const double* h0_offdiag, const double* controllers_dev, const unsigned int* dirnum_dev,
+                                   const unsigned int* shift_dev, long long shift_cstride, int R, long long P, long long skip,
+                                   double sigma, const double* sigma_rows_dev, long long C, long long K, double* fid_out_dev) {
+    if (int rc = check_common(N, in, out, C, K)) return rc;
+    if (N > RC_MAX_NSPIN_SOBOL)
+        return fail(RC_ENOSUP, "Sobol points generated in the fidelity kernel: N <= 13 (longer chains: the two-kernel route, "
+                               "rc_draws_sobol_f64_async + rc_mc_fidelity_f64_async)");
+    if (kernel != RC_KERNEL_AUTO && kernel != RC_KERNEL_TRIDIAG_ADJ)
+        return fail(RC_ENOSUP, "Sobol points generated in the fidelity kernel: the eigenvalue-only chain kernels only (RC_KERNEL_AUTO / "
+                               "RC_KERNEL_TRIDIAG_ADJ; others: the two-kernel route, rc_draws_sobol_f64_async + rc_mc_fidelity_f64_async)");
+    rckp::SobolDraws q;
+    if (int rc = check_sobol(3 * N, dirnum_dev, shift_dev, shift_cstride, R, P, skip, sigma, sigma_rows_dev, C, K, &q)) return rc;
+    if (C == 0 || K == 0) return RC_OK;
+    if (!controllers_dev || !dirnum_dev || !shift_dev || !fid_out_dev) return fail(RC_EINVAL, "NULL array pointer");
+    FidParams p{};
+    p.ctrl = controllers_dev;
+    p.draws = nullptr;
+    p.fid = fid_out_dev;
+    p.C = C;
+    p.K = K;
+    p.draw_cstride = 0;
+    p.tiles_per_ctrl = (K + 63) / 64;
+    p.ntiles = C * p.tiles_per_ctrl;
+    p.in = in;
+    p.out = out;
+    p.align16 = 0;
+    if (p.ntiles > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    RC_HIP_CHECK(hipSetDevice(device));
+    fill_h0(p.h0, N, h0_diag, h0_offdiag);
+    const bool ends = (in == 0 && out == N - 1) || (in == N - 1 && out == 0);     // (same choice as enqueue_fidelity: bit-identical)
+    const hipError_t e = (hipError_t)rc_qmc_fidelity_launch(N, ends ? 1 : 0, stream, &p, &q);
+    if (e != hipSuccess) return fail(RC_EHIP, std::string("rc_qmc_fidelity_launch: ") + hipGetErrorString(e));
+    return RC_OK;
 }
 
 int rc_mc_fidelity_nh_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,

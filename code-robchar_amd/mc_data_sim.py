@@ -841,6 +841,80 @@ class MCDataSim:
         return {"noises": noises.tolist(), "tscale": tscale.tolist(), "tshift": tshift.tolist(), "rim": rim.tolist(),
                 "std": std.tolist(), "worst": worst.tolist(), "window_rim": window.tolist()}
 
+    # ------------------------------------------------------------------ randomised quasi-Monte Carlo metrics
+    def get_qmc_dict(self, training_noise: str = None, noises: np.ndarray = None, algoname=None, replicates: int = 16,
+                     points: int = 1024, seed: int = None) -> dict:
+        """RIM_1 and the standard deviation of the fidelity by RANDOMISED QUASI-MONTE CARLO, with their standard errors, per
+        algorithm, sigma level and controller:
+
+            {algo: {"noises": [L], "rim": [L][C], "rim_se": [L][C], "std": [L][C], "std_se": [L][C], "worst": [L][C]}}   (nested lists)
+
+        `replicates` independently scrambled Sobol point sets of `points` points each (`sobol.scramble(3 N, replicates, seed)`,
+        seed default: the instance's): `rim` / `std` are the means over the replicates of each replicate's RIM_1 / standard
+        deviation (centre values of `backend.reduce_metrics`), `rim_se` / `std_se` the standard deviation of those replicate
+        values (ddof = 1) / sqrt(replicates), `worst` the smallest fidelity over all replicates.  Per algorithm ONE launch over
+        the L * C' rows - the controller rows tiled L times, one sigma per row (`noise_model.fidelity_rqmc_replicates`); the
+        scramble is shared by all rows, so controllers and levels are compared on common points.  Controllers padded up to
+        `numcontrollers` are NaN.  Neither NumPy's global stream nor the instance's Philox offset is consumed.
+
+        Cached as JSON in `get_mcname(...) + "q"` together with `replicates`, `points` and `seed`; the file is reused only when
+        all match (and not written with cache_format="none").  One GPU: raises NotImplementedError under an initialised process
+        group or with `devices=...`."""
+        if self.devices is not None:
+            raise NotImplementedError("get_qmc_dict runs on one GPU (devices=... is not supported)")
+        try:
+            import torch.distributed as dist
+            grouped = dist.is_available() and dist.is_initialized()
+        except ImportError:
+            grouped = False
+        if grouped:
+            raise NotImplementedError("get_qmc_dict runs on one GPU (not under an initialised process group)")
+        if isinstance(algoname, str):
+            algos = [algoname]
+        elif algoname is None:
+            algos = list(self.algos)
+        else:
+            algos = list(algoname)
+        if noises is None:
+            noises = self.noises
+        if training_noise is None:
+            training_noise = self.training_noise
+        noises = np.asarray(noises, dtype=np.float64).reshape(-1)
+        R, P = int(replicates), int(points)
+        if R < 2 or P < 1 or P % 64:
+            raise ValueError("replicates must be at least 2 and points a positive multiple of 64")
+        key = {"replicates": R, "points": P, "seed": int(self.seed if seed is None else seed)}
+        path = self.get_mcname(training_noise, noises) + "q"
+        table = {}
+        if os.path.exists(path):
+            with open(path, "rb") as fh:
+                cached = json.load(fh)
+            if isinstance(cached, dict) and all(cached.get(k) == v for k, v in key.items()):
+                table = cached.get("qmc", {})
+        missing = [name for name in algos if name not in table]
+        for name in missing:
+            table[name] = self._qmc_of_algo(name, noises, training_noise, R, P, key["seed"])
+        if missing and self.cache_format != "none":
+            with open(path, "w") as fh:
+                json.dump({**key, "qmc": table}, fh)
+        return {name: table[name] for name in algos}
+
+    def _qmc_of_algo(self, algoname: str, noises: np.ndarray, training_noise, R: int, P: int, seed: int) -> dict:
+        """One algorithm of `get_qmc_dict`: NaN-padded (L, C) tables as nested lists."""
+        L, C, N = int(noises.size), self.numcontrollers, self.Nspin
+        rows_all = self._controller_rows(algoname, training_noise)
+        nvalid = min(len(rows_all), C)
+        ctrl = np.asarray(rows_all[:nvalid], dtype=np.float64).reshape(nvalid, N + 1)
+        out = {k: np.full((L, C), np.nan) for k in ("rim", "rim_se", "std", "std_se", "worst")}
+        if nvalid and L:
+            rep = self.noise_model.fidelity_rqmc_replicates(np.tile(ctrl, (L, 1)), R, P, seed, sigma=np.repeat(noises, nvalid))
+            for name, src in (("rim", "rim1"), ("std", "std")):
+                v = np.asarray(rep[src], dtype=np.float64).reshape(L, nvalid, R)
+                out[name][:, :nvalid] = v.mean(axis=2)
+                out[name + "_se"][:, :nvalid] = v.std(axis=2, ddof=1) / np.sqrt(R)
+            out["worst"][:, :nvalid] = np.asarray(rep["min"], dtype=np.float64).reshape(L, nvalid, R).min(axis=2)
+        return {"noises": noises.tolist(), **{k: v.tolist() for k, v in out.items()}}
+
     # ------------------------------------------------------------------ bootstrap error bars of the metrics
     def get_bootstrap_dict(self, training_noise: str = None, noises: np.ndarray = None, algoname=None, n_boot: int = 1000,
                            conf: float = 0.95, seed: int = None) -> dict:

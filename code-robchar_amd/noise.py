@@ -458,6 +458,45 @@ class noise_model_base:
         couplings only."""
         return self._moments_of_one_launch(backend.mc_fidelity_grad_philox, controllers, n_draws, seed, sigma, offset, shared)
 
+    def fidelity_rqmc(self, controllers, replicates: int = 16, points: int = 1024, seed: int = 0, sigma=None, skip: int = 0,
+                      shared: bool = True):
+        """Randomised quasi-Monte Carlo estimate of the mean fidelity of every controller row, with its standard error: `replicates`
+        independently scrambled Sobol point sets (`sobol.scramble(3 N, replicates, seed)`: linear matrix scrambling + digital shift)
+        of `points` points each -> {"mean": (C,), "se": (C,), "replicate_means": (C, R)}, se = std of the R replicate means
+        (ddof = 1) / sqrt(R).  ONE fidelity launch - `backend.mc_fidelity_sobol` for chains of N <= 13 spins, the generator
+        `backend.sobol_normal` + the tensor kernel otherwise - plus `backend.reduce_metrics` on the (C R, P) view of fid (C, R P).
+        `sigma`: None = the model's current level; a float; or one value per controller row.  shared=True: every row reads the
+        same shifts (common random numbers); False: a shift row per controller.  NumPy arrays out."""
+        rep = self.fidelity_rqmc_replicates(controllers, replicates, points, seed, sigma=sigma, skip=skip, shared=shared)
+        means = 1.0 - rep["rim1"]
+        return {"mean": means.mean(axis=1), "se": means.std(axis=1, ddof=1) / np.sqrt(means.shape[1]), "replicate_means": means}
+
+    def fidelity_rqmc_replicates(self, controllers, replicates: int, points: int, seed: int, sigma=None, skip: int = 0,
+                                 shared: bool = True):
+        """The launch behind `fidelity_rqmc`: per controller row and scrambled replicate the centre metrics of
+        `backend.reduce_metrics` over the replicate's `points` fidelities -> {"rim1", "std", "min"}, each a (C, R) NumPy array."""
+        from . import sobol
+        diag, off, ring, imag = self._static_terms()
+        R, P, N = int(replicates), int(points), self.Nspin
+        if R < 2:
+            raise ValueError("replicates must be at least 2 (the standard error is taken over them)")
+        if sigma is None:
+            sigma = float(self.rng.args.get("scale", self.noise))
+        if not backend._is_torch(controllers):
+            controllers = np.asarray(controllers, dtype=np.float64).reshape(-1, N + 1)
+        C = int(controllers.shape[0])
+        dirnum, shift = sobol.scramble(3 * N, R, seed, C=None if shared else C)
+        if backend.sobol_fused_supported(N, ring) and not imag.any():
+            fid = backend.mc_fidelity_sobol(controllers, R * P, N, self.inspin, self.outspin, dirnum, shift, P, skip=skip, sigma=sigma,
+                                            h0_diag=diag, h0_offdiag=off)
+        else:
+            draws = backend.sobol_normal(dirnum, shift, P, R * P, skip=skip, sigma=sigma, C=C, device=self.device, as_torch=True)
+            fid = self.fidelity_from_draws(controllers if backend._is_torch(controllers) else np.ascontiguousarray(controllers),
+                                           draws.view(C, R * P, N, 3))
+        red = backend.reduce_metrics(fid.reshape(C * R, P), q_thresholds=(), overlapped=False)
+        host = lambda v: v.cpu().numpy() if backend._is_torch(v) else np.asarray(v)
+        return {k: host(red[k])[0].reshape(C, R) for k in ("rim1", "std", "min")}
+
     def fidelity_jitter_moments_philox(self, controllers, n_draws: int, seed: int, sigma_t: float, order: int = 8, sigma=None,
                                        offset: int = 0, shared: bool = False):
         """`fidelity_moments_philox` of the fidelity AVERAGED OVER A GAUSSIAN READOUT-TIME JITTER of standard deviation `sigma_t`:

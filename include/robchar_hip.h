@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 18     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 19     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -75,7 +75,9 @@ extern "C" {
                                   16: + rc_mc_fidelity_times_f64_async, rc_mc_fidelity_times_f64,
                                       rc_mc_fidelity_times_philox_f64_async, rc_stats_times_general_tiles, RC_MAX_TIMES (additive);
                                   17: + rc_mc_fidelity_grad_times_philox_f64_async (additive);
-                                  18: + rc_wasserstein_matrix_f64_async, rc_wasserstein_matrix_f64 (additive) */
+                                  18: + rc_wasserstein_matrix_f64_async, rc_wasserstein_matrix_f64 (additive);
+                                  19: + rc_sobol_dirnum_u32, rc_draws_sobol_f64_async, rc_draws_sobol_f64,
+                                      rc_mc_fidelity_sobol_f64_async, RC_SOBOL_MAX_DIM, RC_MAX_NSPIN_SOBOL (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -87,6 +89,9 @@ extern "C" {
 #define RC_MAX_NSPIN_GRAD 12   /* (ABI 7) limit of the fidelity-gradient kernel (chain topology).  Its QL carries eigenvector rows in
                                  * registers: all N up to N = 9, batches of 6 / 5 / 4 rows in 2 / 3 / 5 passes at N = 10 / 11 / 12; the
                                  * pass count, not a register limit, is what ends the list here */
+
+#define RC_SOBOL_MAX_DIM 96    /* (ABI 19) dimensions of the Sobol table: the 3 N coordinates of chains of up to 32 spins */
+#define RC_MAX_NSPIN_SOBOL 13  /* (ABI 19) limit of the fidelity kernel that generates its Sobol normals itself (chain topology) */
 
 #define RC_OK 0
 #define RC_EINVAL (-1)   /* bad argument (N out of range, in/out out of range, NULL pointer, ...) */
@@ -640,6 +645,39 @@ int rc_draws_philox_f64(int device, unsigned long long seed, unsigned long long 
                         double* out);
 int rc_draws_philox_f64_async(int device, void* stream, unsigned long long seed, unsigned long long offset,
                               long long n, double scale, double* out_dev);
+
+/* (ABI 19) Randomised quasi-Monte Carlo: scrambled Sobol points and their normals.  code-robchar_amd/sobol.py (NumPy only) is the
+ * DEFINITION; the device reproduces its integer points bit for bit and its normals to a few ulp.
+ *   point    dimension d, index n (0 <= n < 2^32), direction numbers v[d][0..31] (uint32, bit 31 = first binary digit):
+ *            x = XOR over the set bits j of gray(n) = n ^ (n >> 1) of v[d][j], then x ^= shift[d]   (SciPy's and torch's order)
+ *   normal   u = (x + 0.5) 2^-32 in (0, 1);  z = Phi^-1(u) by Wichura's AS 241 (PPND16), |z| <= 6.34, z(~x) == -z(x) exactly;
+ *            draw = fl(sigma z), one rounded product
+ *   samples  sample k of controller row c belongs to replicate r = k / P and is point n = skip + (k mod P) of that replicate;
+ *            tables dirnum[R][D][32] and shift[Cs][R][D], the shifts read at row c when shift_cstride = R D and at row 0 when
+ *            shift_cstride = 0 (common random numbers across controllers)
+ *   contract 1 <= D <= RC_SOBOL_MAX_DIM, R >= 1, K <= R P, skip % 64 == 0, P % 64 == 0 whenever R > 1, skip + min(P, K) <= 2^32,
+ *            shift_cstride 0 or R D; anything else is RC_EINVAL.  C == 0 or K == 0: RC_OK, nothing written.
+ * rc_sobol_dirnum_u32: host only, no HIP call - the unscrambled Joe-Kuo table out_host[D][32] of the first D dimensions (a C client
+ * scrambles it as sobol.py's `scramble` does, or uses it as it is with zero shifts).
+ * rc_draws_sobol_f64_async: draws_out_dev [C][K][D] fp64 = sigma_c z (sigma_rows_dev[c], or `sigma` when that is NULL) and
+ * bits_out_dev [C][K][D] uint32 = the points x; either may be NULL, not both.  For D = 3 N the draws are the [C][K][N][3] tensor
+ * every entry that reads draws takes.  No atomics: same inputs, same bits.  rc_draws_sobol_f64: the blocking twin, host or device
+ * pointers. */
+int rc_sobol_dirnum_u32(int D, unsigned int* out_host);
+int rc_draws_sobol_f64_async(int device, void* stream, int D, const unsigned int* dirnum_dev, const unsigned int* shift_dev,
+                             long long shift_cstride, int R, long long P, long long skip, double sigma, const double* sigma_rows_dev,
+                             long long C, long long K, double* draws_out_dev, unsigned int* bits_out_dev);
+int rc_draws_sobol_f64(int device, int D, const unsigned int* dirnum, const unsigned int* shift, long long shift_cstride, int R,
+                       long long P, long long skip, double sigma, const double* sigma_rows, long long C, long long K,
+                       double* draws_out, unsigned int* bits_out);
+/* The chain fidelity kernel with the Sobol normals generated inside it (D = 3 N, dimension 3 i + s for site i, slot s): no draw
+ * tensor.  BIT-IDENTICAL to rc_draws_sobol_f64_async followed by rc_mc_fidelity_f64_async(RC_KERNEL_AUTO) on that tensor.  Chain
+ * topology, N = 2 .. RC_MAX_NSPIN_SOBOL, RC_KERNEL_AUTO / RC_KERNEL_TRIDIAG_ADJ; everything else is RC_ENOSUP (use the two-kernel
+ * route).  A NaN controller row gives NaN. */
+int rc_mc_fidelity_sobol_f64_async(int device, void* stream, int kernel, int N, int in, int out, const double* h0_diag,
+                                   const double* h0_offdiag, const double* controllers_dev, const unsigned int* dirnum_dev,
+                                   const unsigned int* shift_dev, long long shift_cstride, int R, long long P, long long skip,
+                                   double sigma, const double* sigma_rows_dev, long long C, long long K, double* fid_out_dev);
 
 /* The reference's OWN random stream on the device: NumPy's legacy `RandomState` normal generator (MT19937 + polar
  * Box-Muller, what `np.random.normal` at noise_model.py:114-115 draws from), continued from `state` - the caller's
