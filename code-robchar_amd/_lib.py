@@ -36,6 +36,7 @@ EXPORTS = (
     "rc_stats_times_general_tiles", "rc_mc_fidelity_grad_times_philox_f64_async",
     "rc_wasserstein_matrix_f64_async", "rc_wasserstein_matrix_f64",
     "rc_sobol_dirnum_u32", "rc_draws_sobol_f64_async", "rc_draws_sobol_f64", "rc_mc_fidelity_sobol_f64_async",
+    "rc_mc_fidelity_pickfreeze_philox_f64_async",
 )
 
 RC_KERNEL_AUTO, RC_KERNEL_TRIDIAG_QL, RC_KERNEL_JACOBI, RC_KERNEL_TRIDIAG_ADJ, RC_KERNEL_EXPM, RC_KERNEL_RING_HH = 0, 1, 2, 3, 4, 5
@@ -192,6 +193,7 @@ def load():
     lib.rc_draws_sobol_f64_async.argtypes = [i, vp, i, dp, dp, ll, i, ll, ll, dbl, dp, ll, ll, dp, dp]
     lib.rc_draws_sobol_f64.argtypes = [i, i, dp, dp, ll, i, ll, ll, dbl, dp, ll, ll, dp, dp]
     lib.rc_mc_fidelity_sobol_f64_async.argtypes = [i, vp, i, i, i, i, dp, dp, dp, dp, dp, ll, i, ll, ll, dbl, dp, ll, ll, dp]
+    lib.rc_mc_fidelity_pickfreeze_philox_f64_async.argtypes = [i, vp, i, i, i, i, dp, dp, dp, ull, ull, ull, dbl, dp, dp, i, ll, ll, dp, dp]
     _lib = lib
     return lib
 

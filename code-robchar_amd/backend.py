@@ -1512,3 +1512,58 @@ def mc_fidelity_sobol(controllers, n_draws: int, nspin: int, inspin: int, outspi
                                                   _dev_ptr(ctrl), _dev_ptr(dn), _dev_ptr(sh), stride, R, int(P), int(skip),
                                                   draw_args[2], draw_args[3], C, K, _dev_ptr(out)))
     return out
+
+
+# ---- variance indices (ABI 20): the pick-freeze kernel; variance_indices.py is the definition ------------------------------------
+PICKFREEZE_OUTPUTS = ("fid", "mean")
+MAX_NSPIN_PICKFREEZE = 13            # RC_MAX_NSPIN_PICKFREEZE
+
+
+def pickfreeze_supported(nspin: int, ring: bool = False, kernel: str = "auto") -> bool:
+    """Can `mc_fidelity_pickfreeze_philox` take this geometry (chain, N <= 13, eigenvalue-only kernels)?"""
+    return (not ring) and 2 <= nspin <= MAX_NSPIN_PICKFREEZE and kernel in ("auto", "tridiag_adj")
+
+
+def mc_fidelity_pickfreeze_philox(controllers, n_draws: int, nspin: int, inspin: int, outspin: int, seed: int, groups,
+                                  offset: int = 0, offset_b=None, sigma=0.05, h0_diag=None, h0_offdiag=None, want=("mean",),
+                                  kernel: str = "auto"):
+    """The pick-freeze evaluations behind the variance indices in ONE launch (`rc_mc_fidelity_pickfreeze_philox_f64_async`;
+    `variance_indices` is the definition): per sample two draw vectors a (stream block at `offset`: the draws of
+    `mc_fidelity_philox`) and b (at `offset_b`; None = the block behind a's, offset + C K 3N) are generated inside the kernel and
+    the fidelity is evaluated on a, on b and on the G hybrids "b where `groups[g]` has the coordinate's bit, a elsewhere".
+    controllers (C, N+1) torch CUDA tensor (a NumPy array is uploaded to the current device) -> dict of torch tensors on that
+    device, the entries named in `want`, enqueued on the current stream:
+
+        "fid"  (G + 2, C, K)   slab 0 = F(a), 1 = F(b), 2 + g = F(h_g): bit-identical to `mc_fidelity_philox` at the two offsets and
+                               to `mc_fidelity` on `torch.where(mask_g, B, A)` of the two `philox_normal` tensors,
+        "mean" (C, 3 + 2 G)    the means over k of F(a), F(b), D = (F(a) - F(b))^2 and per group T_g = (F(a) - F(h_g))^2,
+                               U_g = (F(b) - F(h_g))^2  (`variance_indices.indices_from_means`: var = D / 2, total_g = T_g / D,
+                               first_g = 1 - U_g / D); the same bits with or without "fid".
+
+    `groups`: at most 64 uint64 masks over the coordinates 3 i + s (`variance_indices.kind_groups` ...); `sigma`: a float, or a
+    (C,) tensor / array.  Chain topology, N <= 13, kernel "auto" / "tridiag_adj".  Everything is validated before the device is
+    touched."""
+    from . import variance_indices as vi
+    _check_geometry(nspin, inspin, outspin)
+    want = _check_want(want, PICKFREEZE_OUTPUTS)
+    if kernel not in _lib.KERNELS:
+        raise ValueError(f"kernel: one of {tuple(_lib.KERNELS)}")
+    if not pickfreeze_supported(nspin, False, kernel):
+        raise NotImplementedError("the pick-freeze kernel takes chains of N <= 13 spins and the kernels \"auto\" / \"tridiag_adj\" "
+                                  "(otherwise: variance_indices on mc_fidelity outputs of the hybrid tensors)")
+    masks = vi.check_groups(groups, nspin)
+    G = int(masks.shape[0])
+    h0d, h0o = _static_terms(h0_diag, h0_offdiag, nspin)
+    nrows = int(controllers.shape[0]) if hasattr(controllers, "shape") else len(controllers)
+    offset = int(offset) % 2 ** 64
+    offset_b = vi.default_offset_b(offset, nrows, n_draws, nspin) if offset_b is None else int(offset_b) % 2 ** 64
+    if int(n_draws) >= 0 and not vi.ranges_disjoint(offset, offset_b, nrows * int(n_draws) * 3 * nspin):
+        raise ValueError("offset_b: the element ranges of offset and offset_b overlap (each covers C K 3N elements)")
+    ctrl, rows, C, K, draw_args = _generated_draws_args(controllers, n_draws, sigma, seed, offset, nspin)
+    lib = _lib.load()
+    dev = ctrl.device
+    res, out_ptr = _outputs(PICKFREEZE_OUTPUTS, want, {"fid": (G + 2, C, K), "mean": (C, 3 + 2 * G)}, dev)
+    _lib.check(lib.rc_mc_fidelity_pickfreeze_philox_f64_async(
+        *_on_stream(dev), _lib.KERNELS[kernel], nspin, inspin, outspin, _ptr(h0d), _ptr(h0o), _dev_ptr(ctrl), draw_args[0], draw_args[1],
+        offset_b, draw_args[2], draw_args[3], _ptr(masks) if G else None, G, C, K, *out_ptr))
+    return res

@@ -198,4 +198,25 @@ struct SobolDraws {
     int R, D;
 };
 
+// pick-freeze kernel of the variance indices (k_fidelity_pickfreeze.inc.h; the definition: code-robchar_amd/variance_indices.py):
+// FidParams' geometry without a draw tensor and TWO draw vectors per sample - coordinate j = 3 i + s of sample (c, k) is element
+// offset_a (offset_b) + (c K + k) 3 N + j  of stream `seed` -; evaluation e = 0 takes a, e = 1 takes b, e = 2 + g takes b where
+// groups[g] has bit j set and a elsewhere.
+struct PickFreezeParams {
+    const double* ctrl;    // [C][N+1]
+    double* fid;           // [G+2][C][K] or NULL
+    double* part;          // [ntiles][3+2G] per-tile sums for the row means, or NULL
+    long long C, K;
+    long long tiles_per_ctrl;
+    long long ntiles;
+    int in, out;
+    int G;                            // number of groups, 0 .. RC_PICKFREEZE_MAX_GROUPS
+    unsigned long long seed;
+    unsigned long long offset_a, offset_b;
+    const double* sigma_rows;         // [C] scale per controller row, or NULL: `sigma` for all
+    double sigma;
+    StaticH h0;
+    unsigned long long groups[RC_PICKFREEZE_MAX_GROUPS];   // by value: no device copy, no lifetime obligation for the caller
+};
+
 }  // namespace rckp

@@ -90,6 +90,10 @@ __attribute__((visibility("hidden"))) int rc_qmc_draws_launch(void* stream, cons
 __attribute__((visibility("hidden"))) int rc_qmc_fidelity_launch(int N, int ends, void* stream, const rckp::FidParams* p,
                                                                  const rckp::SobolDraws* q);
 __attribute__((visibility("hidden"))) int rc_qmc_counter_addr(int which, void** addr);
+// sixth translation unit (robchar_vidx.hip): the pick-freeze fidelity kernel of the variance indices and its row means
+__attribute__((visibility("hidden"))) int rc_vidx_pickfreeze_launch(int N, int ends, void* stream, const rckp::PickFreezeParams* p,
+                                                                    double* mean);
+__attribute__((visibility("hidden"))) int rc_vidx_counter_addr(int which, void** addr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1376,7 +1380,7 @@ void run_gather_share_locked(GatherJob* j) {
 // Sum of a diagnostic tile counter (synchronises the device; optionally zeroes it): `slots` unsigned 64-bit counters at each of
 // the n device addresses addr_of[u]() gives (a hipError_t).  `what`: the text of any failure; NULL: a counter of the chain /
 // ring kernels - this unit's copy, then the second unit's (robchar_large.hip: chains of 17 .. 24 spins, rings of 11 .. 16) and
-// the Sobol fidelity kernel's (robchar_qmc.hip) -,
+// the Sobol fidelity kernel's (robchar_qmc.hip) and the pick-freeze kernel's (robchar_vidx.hip) -,
 // whose texts say what failed and in which unit.
 typedef int (*CounterAddr)(void**);
 static long long read_tile_counter(int device, int reset, const CounterAddr* addr_of, int n, int slots, const char* what) {
@@ -1387,7 +1391,8 @@ static long long read_tile_counter(int device, int reset, const CounterAddr* add
     const size_t nb = sizeof(unsigned long long) * slots;
     unsigned long long sum = 0;
     for (int u = 0; u < n; ++u) {
-        const std::string unit = u == 0 ? " the tile counter failed" : u == 1 ? " the tile counter (second unit) failed" : " the tile counter (Sobol unit) failed";
+        const std::string unit = u == 0 ? " the tile counter failed" : u == 1 ? " the tile counter (second unit) failed"
+                                 : u == 2 ? " the tile counter (Sobol unit) failed" : " the tile counter (variance-index unit) failed";
         unsigned long long v[64] = {0};
         void* addr = nullptr;
         if ((u == 0 && hipDeviceSynchronize() != hipSuccess) || addr_of[u](&addr) != hipSuccess || !addr ||
@@ -1579,16 +1584,18 @@ int rc_device_count(void) {
 const char* rc_last_error(void) { return g_last_error.c_str(); }
 
 long long rc_stats_general_tiles(int device, int reset) {
-    const CounterAddr units[3] = {[](void** a) { return (int)hipGetSymbolAddress(a, HIP_SYMBOL(g_general_tiles)); },
+    const CounterAddr units[4] = {[](void** a) { return (int)hipGetSymbolAddress(a, HIP_SYMBOL(g_general_tiles)); },
                                   [](void** a) { return rc_large_counter_addr(0, a); },
-                                  [](void** a) { return rc_qmc_counter_addr(0, a); }};
-    return read_tile_counter(device, reset, units, 3, 1, nullptr);
+                                  [](void** a) { return rc_qmc_counter_addr(0, a); },
+                                  [](void** a) { return rc_vidx_counter_addr(0, a); }};
+    return read_tile_counter(device, reset, units, 4, 1, nullptr);
 }
 long long rc_stats_polish_tiles(int device, int reset) {
-    const CounterAddr units[3] = {[](void** a) { return (int)hipGetSymbolAddress(a, HIP_SYMBOL(g_polish_tiles)); },
+    const CounterAddr units[4] = {[](void** a) { return (int)hipGetSymbolAddress(a, HIP_SYMBOL(g_polish_tiles)); },
                                   [](void** a) { return rc_large_counter_addr(1, a); },
-                                  [](void** a) { return rc_qmc_counter_addr(1, a); }};
-    return read_tile_counter(device, reset, units, 3, 64, nullptr);
+                                  [](void** a) { return rc_qmc_counter_addr(1, a); },
+                                  [](void** a) { return rc_vidx_counter_addr(1, a); }};
+    return read_tile_counter(device, reset, units, 4, 64, nullptr);
 }
 
 int rc_set_fidelity_kernel(int kernel) {
@@ -2420,6 +2427,49 @@ int rc_mc_fidelity_sobol_f64_async(int device, void* stream, int kernel, int N, 
     const hipError_t e = (hipError_t)rc_qmc_fidelity_launch(N, ends ? 1 : 0, stream, &p, &q);
     if (e != hipSuccess) return fail(RC_EHIP, std::string("rc_qmc_fidelity_launch: ") + hipGetErrorString(e));
     return RC_OK;
+}
+
+// ---- variance indices (ABI 20): the pick-freeze kernel, code-robchar_amd/variance_indices.py is the definition --------------------
+int rc_mc_fidelity_pickfreeze_philox_f64_async(int device, void* stream, int kernel, int N, int in, int out, const double* h0_diag,
+                                               const double* h0_offdiag, const double* controllers_dev, unsigned long long seed,
+                                               unsigned long long offset_a, unsigned long long offset_b, double sigma,
+                                               const double* sigma_rows_dev, const unsigned long long* groups, int G, long long C,
+                                               long long K, double* fid_out_dev, double* mean_out_dev) {
+    if (int rc = check_common(N, in, out, C, K)) return rc;
+    if (N > RC_MAX_NSPIN_PICKFREEZE)
+        return fail(RC_ENOSUP, "pick-freeze kernel: N <= 13 (longer chains: rc_draws_philox_f64_async, the hybrids and "
+                               "rc_mc_fidelity_f64_async, with variance_indices.py on their outputs)");
+    if (kernel != RC_KERNEL_AUTO && kernel != RC_KERNEL_TRIDIAG_ADJ)
+        return fail(RC_ENOSUP, "pick-freeze kernel: the eigenvalue-only chain kernels only (RC_KERNEL_AUTO / RC_KERNEL_TRIDIAG_ADJ)");
+    if (G < 0 || G > RC_PICKFREEZE_MAX_GROUPS) return fail(RC_EINVAL, "G must be in [0, 64]");
+    if (G > 0 && !groups) return fail(RC_EINVAL, "NULL array pointer (groups)");
+    for (int g = 0; g < G; ++g)
+        if (groups[g] >> (3 * N))
+            return fail(RC_EINVAL, "group " + std::to_string(g) + ": a mask bit at or above 3 N = " + std::to_string(3 * N));
+    if (!sigma_rows_dev && !(sigma >= 0.0 && sigma < HUGE_VAL))
+        return fail(RC_EINVAL, "sigma must be finite and non-negative (or give sigma_rows)");
+    // the two element ranges [offset, offset + C K 3N) as distances modulo 2^64 (a wrapping offset is legal)
+    const unsigned long long len = (unsigned long long)C * (unsigned long long)K * (unsigned long long)(3 * N);
+    if (len && (offset_b - offset_a < len || offset_a - offset_b < len))
+        return fail(RC_EINVAL, "the element ranges of offset_a and offset_b overlap (each covers C K 3N elements)");
+    if (!fid_out_dev && !mean_out_dev) return fail(RC_EINVAL, "no output requested (fid_out and mean_out are both NULL)");
+    if (C == 0 || K == 0) return RC_OK;
+    if (!controllers_dev) return fail(RC_EINVAL, "NULL array pointer (controllers)");
+    rckp::PickFreezeParams p{};
+    fill_deriv_params(p, N, in, out, h0_diag, h0_offdiag, controllers_dev, C, K, fid_out_dev);
+    if (p.ntiles > 0x7fffffffLL) return fail(RC_EINVAL, "too many tiles for one launch");
+    p.G = G;
+    p.seed = seed;
+    p.offset_a = offset_a;
+    p.offset_b = offset_b;
+    p.sigma_rows = sigma_rows_dev;
+    p.sigma = sigma;
+    for (int g = 0; g < G; ++g) p.groups[g] = groups[g];
+    RC_HIP_CHECK(hipSetDevice(device));
+    hipStream_t s = (hipStream_t)stream;
+    const bool ends = (in == 0 && out == N - 1) || (in == N - 1 && out == 0);     // (same choice as enqueue_fidelity: bit-identical)
+    return launch_with_part(s, p, mean_out_dev != nullptr, 3 + 2 * G, "rc_vidx_pickfreeze_launch",
+                            [&] { return rc_vidx_pickfreeze_launch(N, ends ? 1 : 0, (void*)s, &p, mean_out_dev); });
 }
 
 int rc_mc_fidelity_nh_f64_async(int device, void* stream, int N, int in, int out, const double* h0_diag,

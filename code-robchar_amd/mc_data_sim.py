@@ -743,6 +743,91 @@ class MCDataSim:
                 direction[j0:j1, :nvalid] = res["direction"].reshape(j1 - j0, nvalid, N, 3)
         return {"noises": noises.tolist(), "fav": fav.tolist(), "dfav_dlogsigma": slope.tolist(), "direction": direction.tolist()}
 
+    # ------------------------------------------------------------------ variance-based sensitivity to the noise sources
+    def get_variance_dict(self, training_noise: str = None, noises: np.ndarray = None, algoname=None, groups="kind",
+                          samples: int = None, seed: int = None, replicates: int = 1) -> dict:
+        """Which noise source is responsible for the spread of the fidelity, and how much of it is interaction between sources:
+        the variance of the fidelity over the structured noise and its first- and total-order indices per group of noise
+        coordinates (`variance_indices` is the definition; the pick-freeze scheme), per algorithm, sigma level and controller:
+
+            {algo: {"noises": [L], "groups": [G], "fav": [L][C], "var": [L][C], "first": [L][C][G], "total": [L][C][G]}}
+                                                                                                          (nested lists)
+
+        `groups`: "kind" (all site energies / real / imaginary couplings), "site", "direction" (the 3 N - 2 single coordinates)
+        or a list of masks over the coordinates 3 i + s; "groups" in the result names them.  `first` is what the group explains
+        on its own, `total` adds every interaction it takes part in; `var` = Var F, `fav` the mean fidelity, over K = `samples`
+        (default: `bootreps`) pairs of draw vectors at the level.  A sigma = 0 level has var = 0 and NaN indices; controllers
+        padded up to `numcontrollers` are NaN.  replicates = R >= 2 adds "var_se", "first_se", "total_se": the values are then
+        the means over R independent replicates and these their standard errors.
+
+        Draws as in `get_sensitivity_dict`: counter-based, generated inside the kernel (`noise_model.noise_variance_indices_philox`)
+        whatever `rng_mode` says, stream `seed` (default: the instance's), per algorithm ONE launch over the R * L * C' rows - the
+        controller rows tiled, one sigma per row.  Replicate r, level j, controller c, draw k, coordinate 3 i + s reads its first
+        vector at stream element (((r L + j) C' + c) K + k) 3 N + 3 i + s and its second one R L C' K 3 N elements further on; the
+        offsets start at 0 for EVERY algorithm.  Neither NumPy's global stream nor the instance's Philox offset is consumed.
+
+        Cached as JSON in `get_mcname(...) + "v"` together with `samples`, `seed`, the group masks and `replicates`; the file is
+        reused only when all match (and not written with cache_format="none").  One GPU: raises NotImplementedError under an
+        initialised process group or with `devices=...`."""
+        from . import variance_indices as vi
+        if self.devices is not None:
+            raise NotImplementedError("get_variance_dict runs on one GPU (devices=... is not supported)")
+        try:
+            import torch.distributed as dist
+            grouped = dist.is_available() and dist.is_initialized()
+        except ImportError:
+            grouped = False
+        if grouped:
+            raise NotImplementedError("get_variance_dict runs on one GPU (not under an initialised process group)")
+        if isinstance(algoname, str):
+            algos = [algoname]
+        elif algoname is None:
+            algos = list(self.algos)
+        else:
+            algos = list(algoname)
+        if noises is None:
+            noises = self.noises
+        if training_noise is None:
+            training_noise = self.training_noise
+        noises = np.asarray(noises, dtype=np.float64).reshape(-1)
+        masks, labels = vi.named_groups(groups, self.Nspin)
+        K = int(self.bootreps if samples is None else samples)
+        seed = int(self.seed if seed is None else seed)
+        R = int(replicates)
+        if R < 1:
+            raise ValueError("replicates must be at least 1")
+        key = {"samples": K, "seed": seed, "masks": [int(m) for m in masks], "replicates": R}
+        path = self.get_mcname(training_noise, noises) + "v"
+        table = {}
+        if os.path.exists(path):
+            with open(path, "rb") as fh:
+                cached = json.load(fh)
+            if isinstance(cached, dict) and all(cached.get(k) == v for k, v in key.items()):
+                table = cached.get("variance", {})
+        missing = [a for a in algos if a not in table]
+        for name in missing:
+            table[name] = self._variance_of_algo(name, noises, training_noise, K, seed, masks, labels, R)
+        if missing and self.cache_format != "none":
+            with open(path, "w") as fh:
+                json.dump({**key, "variance": table}, fh)
+        return {name: table[name] for name in algos}
+
+    def _variance_of_algo(self, algoname: str, noises: np.ndarray, training_noise, K: int, seed: int, masks, labels, R: int) -> dict:
+        """One algorithm of `get_variance_dict`: NaN-padded (L, C) / (L, C, G) tables as nested lists."""
+        L, C, N, G = int(noises.size), self.numcontrollers, self.Nspin, len(labels)
+        rows_all = self._controller_rows(algoname, training_noise)
+        nvalid = min(len(rows_all), C)
+        ctrl = np.asarray(rows_all[:nvalid], dtype=np.float64).reshape(nvalid, N + 1)
+        names = ("var", "first", "total") + (("var_se", "first_se", "total_se") if R > 1 else ())
+        out = {k: np.full((L, C) if k.startswith("var") else (L, C, G), np.nan) for k in names}
+        out["fav"] = np.full((L, C), np.nan)
+        if nvalid and K and L:
+            res = self.noise_model.noise_variance_indices_philox(np.tile(ctrl, (L, 1)), K, seed, groups=masks,
+                                                                 sigma=np.repeat(noises, nvalid), offset=0, replicates=R)
+            for k in out:
+                out[k][:, :nvalid] = res[k].reshape((L, nvalid) + res[k].shape[1:])
+        return {"noises": noises.tolist(), "groups": list(labels), **{k: v.tolist() for k, v in out.items()}}
+
     # ------------------------------------------------------------------ metrics on a grid of readout times
     _READOUT_MAX_SLAB_BYTES = 1 << 30    # device bytes of the M fidelity slabs of one launch of `get_readout_dict`
 

@@ -429,6 +429,59 @@ class noise_model_base:
         return {"fav": mean[:, 0].copy(), "dfav_dlogsigma": mean[:, 1].copy(),
                 "direction": mean[:, 2:].reshape(-1, self.Nspin, 3).copy()}
 
+    def noise_variance_indices_philox(self, controllers, n_draws: int, seed: int, groups="kind", sigma=None, offset: int = 0,
+                                      replicates: int = 1):
+        """Which noise source is responsible for the spread of the fidelity: the variance-based (first- and total-order) indices
+        of groups of noise coordinates by the pick-freeze scheme (`variance_indices` is the definition), from ONE
+        `backend.mc_fidelity_pickfreeze_philox` launch over `n_draws` pairs of counter-based draw vectors per controller:
+            "fav" (C,) mean fidelity, "var" (C,) its variance over the noise, "first" / "total" (C, G) the indices of every group,
+            "groups" (G,) the uint64 masks ("labels": their names).
+        `groups`: "direction" (the 3 N - 2 single coordinates), "kind" (site / real / imaginary), "site", or an array of masks over
+        the coordinates 3 i + s.  `sigma`: None = the model's current level; a float; or one value per controller row.
+        replicates = R >= 2: the rows are tiled R times onto disjoint stream blocks in the same launch - replicate r reads a at
+        offset + r C K 3N and b at offset + (R + r) C K 3N -; the values are the means over the replicates and "var_se", "first_se", "total_se"
+        their standard errors std(ddof = 1) / sqrt(R).  A sigma = 0 row has var = 0 and NaN indices.  NumPy arrays out.  Chain
+        topology with real static couplings, N <= 13 (otherwise NotImplementedError: `variance_indices` on `mc_fidelity` outputs
+        of the hybrid tensors serves those)."""
+        from . import variance_indices as vi
+        diag, off, ring, imag = self._static_terms()
+        N = self.Nspin
+        if ring:
+            raise NotImplementedError("the variance indices are implemented for the chain topology only")
+        if imag.any():
+            raise NotImplementedError("draws generated inside the pick-freeze kernel: real static couplings only")
+        if not backend.pickfreeze_supported(N, ring):
+            raise NotImplementedError("the pick-freeze kernel takes chains of N <= 13 spins")
+        masks, labels = vi.named_groups(groups, N)
+        R, K = int(replicates), int(n_draws)
+        if R < 1:
+            raise ValueError("replicates must be at least 1")
+        if sigma is None:
+            sigma = float(self.rng.args.get("scale", self.noise))
+        if not backend._is_torch(controllers):
+            controllers = np.asarray(controllers, dtype=np.float64).reshape(-1, N + 1)
+        C = int(controllers.shape[0])
+        per_row = not isinstance(sigma, (int, float)) and np.ndim(sigma) > 0
+        if R > 1:                                    # replicate r = rows r C .. (r + 1) C - 1 of ONE launch
+            tile = (lambda t: t.repeat(R, *([1] * (t.ndim - 1)))) if backend._is_torch(controllers) else (lambda t: np.tile(t, (R,) + (1,) * (t.ndim - 1)))
+            controllers = tile(controllers)
+            if per_row:
+                sigma = sigma.repeat(R) if backend._is_torch(sigma) else np.tile(np.asarray(sigma, dtype=np.float64), R)
+        block = R * C * K * 3 * N                    # a: [offset, offset + block), b: the block behind it
+        mean = backend.mc_fidelity_pickfreeze_philox(controllers, K, N, self.inspin, self.outspin, seed, masks, offset=offset,
+                                                     offset_b=(int(offset) + block) % 2 ** 64, sigma=sigma, h0_diag=diag,
+                                                     h0_offdiag=off, want=("mean",))["mean"]
+        mean = mean.cpu().numpy() if backend._is_torch(mean) else np.asarray(mean)
+        idx = vi.indices_from_means(mean.reshape(R, C, -1))
+        out = {"groups": masks, "labels": labels}
+        if R == 1:
+            out.update({k: idx[k][0].copy() for k in ("fav", "var", "first", "total")})
+            return out
+        out["fav"] = idx["fav"].mean(axis=0)
+        for k in ("var", "first", "total"):
+            out[k], out[k + "_se"] = vi.over_replicates(idx[k])
+        return out
+
     def _moments_of_one_launch(self, launch, controllers, n_draws, seed, sigma, offset, shared):
         """`moments_from_sums` of the "mean" and "moment" rows of one launch of `launch` - `backend.mc_fidelity_grad_philox` or one
         that takes its arguments - with the model's static terms; what `fidelity_moments_philox` and

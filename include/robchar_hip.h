@@ -53,7 +53,7 @@
 extern "C" {
 #endif
 
-#define RC_ABI_VERSION 19     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
+#define RC_ABI_VERSION 20     /* 2: + multi-device entries, legacy-stream draws, JSON cache encoder, RC_KERNEL_RING_HH;
                                   3: + rc_stats_polish_tiles; 4: + rc_directional_draws_legacy_dev;
                                   5: + rc_reserve_ring, rc_release_stream, rc_mc_fidelity_directional_f64_async,
                                      rc_mc_fidelity_philox_f64_async;
@@ -77,7 +77,9 @@ extern "C" {
                                   17: + rc_mc_fidelity_grad_times_philox_f64_async (additive);
                                   18: + rc_wasserstein_matrix_f64_async, rc_wasserstein_matrix_f64 (additive);
                                   19: + rc_sobol_dirnum_u32, rc_draws_sobol_f64_async, rc_draws_sobol_f64,
-                                      rc_mc_fidelity_sobol_f64_async, RC_SOBOL_MAX_DIM, RC_MAX_NSPIN_SOBOL (additive) */
+                                      rc_mc_fidelity_sobol_f64_async, RC_SOBOL_MAX_DIM, RC_MAX_NSPIN_SOBOL (additive);
+                                  20: + rc_mc_fidelity_pickfreeze_philox_f64_async, RC_MAX_NSPIN_PICKFREEZE,
+                                      RC_PICKFREEZE_MAX_GROUPS (additive) */
 #define RC_MAX_NSPIN 32        /* chain topology: register-resident fast kernels for N <= RC_MAX_NSPIN_CHAIN, a general
                                  * LDS-resident per-sample kernel (same arithmetic, ~10x slower per site) above */
 #define RC_MAX_NSPIN_FAST 16   /* limit of the dense kernels (RC_KERNEL_JACOBI, RC_KERNEL_EXPM: ring, non-Hermitian), of the
@@ -92,6 +94,8 @@ extern "C" {
 
 #define RC_SOBOL_MAX_DIM 96    /* (ABI 19) dimensions of the Sobol table: the 3 N coordinates of chains of up to 32 spins */
 #define RC_MAX_NSPIN_SOBOL 13  /* (ABI 19) limit of the fidelity kernel that generates its Sobol normals itself (chain topology) */
+#define RC_MAX_NSPIN_PICKFREEZE 13   /* (ABI 20) limit of the pick-freeze kernel of the variance indices (chain topology) */
+#define RC_PICKFREEZE_MAX_GROUPS 64  /* (ABI 20) groups of noise coordinates per call of that kernel */
 
 #define RC_OK 0
 #define RC_EINVAL (-1)   /* bad argument (N out of range, in/out out of range, NULL pointer, ...) */
@@ -678,6 +682,33 @@ int rc_mc_fidelity_sobol_f64_async(int device, void* stream, int kernel, int N, 
                                    const double* h0_offdiag, const double* controllers_dev, const unsigned int* dirnum_dev,
                                    const unsigned int* shift_dev, long long shift_cstride, int R, long long P, long long skip,
                                    double sigma, const double* sigma_rows_dev, long long C, long long K, double* fid_out_dev);
+
+/* (ABI 20) Variance-based noise sensitivity indices by the pick-freeze scheme.  code-robchar_amd/variance_indices.py (NumPy only)
+ * is the DEFINITION.  Coordinate j = 3 i + s of a sample is slot s of site i in the draw layout [N][3]; a group is a uint64 mask
+ * over the 3 N coordinates (bits >= 3 N must be zero; bits 1 and 2 - the dropped g1_0, g2_0 - are allowed and change nothing).
+ * Per sample (c, k) two draw vectors: a = elements offset_a + ((c K + k) N + i) 3 + s of stream `seed` scaled by sigma (exactly
+ * the draws of rc_mc_fidelity_philox_f64_async), b = the same at offset_b; the two ranges [offset, offset + C K 3N) must be
+ * disjoint (distances modulo 2^64: a wrapping offset is legal).  Hybrid h_g = b where groups[g] has the bit, a elsewhere - a copy
+ * of bits -; fA = F(a), fB = F(b), f_g = F(h_g).
+ *   fid_out_dev  [G + 2][C][K] or NULL: slab 0 = fA, 1 = fB, 2 + g = f_g.  Slab 0 is BIT-IDENTICAL to
+ *                rc_mc_fidelity_philox_f64_async(seed, offset_a), slab 1 to the same at offset_b, slab 2 + g to
+ *                rc_mc_fidelity_f64_async(RC_KERNEL_AUTO) on the materialised hybrid tensor.
+ *   mean_out_dev [C][3 + 2 G] or NULL: the means over k of fA, fB, D = (fA - fB)^2 and, per group, T_g = (fA - f_g)^2 and
+ *                U_g = (fB - f_g)^2 (Jansen's estimators: a difference rounded once, a square rounded once, sums of non-negative
+ *                terms in a fixed order - no atomics: same inputs, same bits, with or without fid_out_dev).  Var F = D / 2,
+ *                total-order index T_g / D, first-order index 1 - U_g / D.  A NaN controller row gives NaN everywhere.
+ * It replaces, for G groups, two rc_draws_philox_f64_async launches, G selections over [C][K][N][3] tensors, G + 2
+ * rc_mc_fidelity_f64_async launches and 2 G + 1 elementwise reductions; no draw tensor exists.  `groups` is a HOST array read
+ * during the call (no device copy, nothing to keep alive).  sigma / sigma_rows_dev as in rc_mc_fidelity_philox_f64_async.
+ * Enqueue-only: never synchronises.  Refused before any HIP call: N outside 2 .. RC_MAX_NSPIN_PICKFREEZE or a kernel other than
+ * RC_KERNEL_AUTO / RC_KERNEL_TRIDIAG_ADJ (RC_ENOSUP), G outside [0, RC_PICKFREEZE_MAX_GROUPS], a mask with a bit >= 3 N,
+ * overlapping element ranges, both outputs NULL, NULL controllers with C > 0, too many tiles (RC_EINVAL).  C == 0 or K == 0: RC_OK
+ * behind the contract, nothing written.  The repair routes count into rc_stats_general_tiles / rc_stats_polish_tiles. */
+int rc_mc_fidelity_pickfreeze_philox_f64_async(int device, void* stream, int kernel, int N, int in, int out, const double* h0_diag,
+                                               const double* h0_offdiag, const double* controllers_dev, unsigned long long seed,
+                                               unsigned long long offset_a, unsigned long long offset_b, double sigma,
+                                               const double* sigma_rows_dev, const unsigned long long* groups, int G, long long C,
+                                               long long K, double* fid_out_dev, double* mean_out_dev);
 
 /* The reference's OWN random stream on the device: NumPy's legacy `RandomState` normal generator (MT19937 + polar
  * Box-Muller, what `np.random.normal` at noise_model.py:114-115 draws from), continued from `state` - the caller's
