@@ -23,7 +23,9 @@ WEIGHTS = np.array([0.1, 0.2, 0.4, 0.2, 0.1])
 SEED, SIGMA = gc.PHILOX_SEED, gc.PHILOX_SIGMA
 EPS = 2.0 ** -52
 OUTPUTS = ("fid", "grad", "mean", "moment")
-SIZES = (2, 3, 7, 9, 10, 12)          # small; the residency edge; the last single pass; the first multi-pass size; the most passes
+# every instantiation: 2 ... 9 single pass (7 the residency edge); 10: the first multi-pass size; 11: the only size with five
+# eigenvector rows per QL pass in three passes (`grad_batch_rows`, `grad_passes`); 12: the most passes
+SIZES = tuple(range(2, 13))
 MIN_BIAS_TEETH, MIN_TIME_TEETH = 0.01, 0.1
 
 

@@ -3,9 +3,9 @@ sample - on the device (the checks of grad_times_checks.py): per-sample outputs 
 `mc_fidelity_grad_philox` combined on the host; the unit grid; row means and moment sums; the independent reference; W against
 the readout-time kernel; u < 0, u = 0, M = 64, hard inputs; and `optimize_controllers(jitter=...)` end to end.  Shapes are the
 smallest that reach each path: C = 3 rows (one NaN, one with a negative time entry), K = 70 = one tile and a tail of 6 (K = 130
-with shared draws), N = 2, 3 (small), 7 (the residency edge), 9 (the last single pass), 10 (the first multi-pass size), 12 (the
-most passes).  ROBCHAR_GRAD_FORCED_GENERAL=1 announces a -DRC_GRAD_FORCE_GENERAL=1 variant build (scripts/build_variant.sh), in
-which every tile takes the sweep-cap fallback."""
+with shared draws), every instantiation N = 2 ... 12 (7: the residency edge, 9: the last single pass, 10: the first multi-pass size,
+11: the only size with five eigenvector rows per QL pass in three passes, 12: the most passes).  ROBCHAR_GRAD_FORCED_GENERAL=1
+announces a -DRC_GRAD_FORCE_GENERAL=1 variant build (scripts/build_variant.sh), in which every tile takes the sweep-cap fallback."""
 import importlib
 import os
 
@@ -36,7 +36,7 @@ def test_per_sample_outputs_are_the_single_time_kernels_bits(be, N):
     counted(be, be.grad_general_tiles(reset=True))
 
 
-@pytest.mark.parametrize("N", (7, 10))
+@pytest.mark.parametrize("N", (7, 10, 11))
 def test_far_offset_and_per_row_sigma(be, N):
     """check 1, continued: offset 2^40 + 3, and one sigma per row with a sigma = 0 row"""
     exact = N not in NOT_BIT_IDENTICAL
@@ -90,7 +90,7 @@ def test_w_against_the_readout_time_kernel(be, N):
     print(f"N = {N}: max |W - wsum of the times kernel| = {worst:.2e}")
 
 
-@pytest.mark.parametrize("N", (3, 7, 12))
+@pytest.mark.parametrize("N", (3, 7, 11, 12))
 def test_semantics_and_hard_inputs(be, N):
     """check 6: every u < 0, u = 0, M = 64; the hard inputs - the product build counts no fallback tile on them"""
     gt.check_semantics(be, N)

@@ -105,8 +105,10 @@ def two_routes(be, dev, ctrl, N, a, b, dirnum, shift, P, K, skip, sigma, **stati
     return got.cpu().numpy(), want.cpu().numpy()
 
 
-@pytest.mark.parametrize("N", (2, 3, 7, 9, 13))
+@pytest.mark.parametrize("N", range(2, 14))
 def test_fused_kernel_is_bit_identical_to_generator_plus_tensor_kernel(be, dev, N):
+    """every instantiation of the fused kernel.  The controllers of seed 5100 + N pass `assert_has_teeth` at every N (on the CPU, the
+    oracle reference below: the smallest median F is 0.196, at N = 11, and every sample is above 1e-3), so no seed had to move."""
     rng = np.random.default_rng(5100 + N)
     C = 4
     ctrl = cc.deloc_ctrl(rng, C, N, 0.5)
@@ -130,6 +132,7 @@ def test_fused_kernel_is_bit_identical_to_generator_plus_tensor_kernel(be, dev, 
     want = orc.fidelity_eigh(good, sobol.normals(dirnum, sh, 128, 200, 64, sigma=sig[[0, 1, 3]]).reshape(3, 200, N, 3), N, 0, N - 1, **static)
     cc.assert_has_teeth(want, what=(N, "sobol"))
     err = np.abs(got - want)
+    print(f"fused Sobol kernel vs oracle, N = {N}: abs {err.max():.1e} rel {(err[want > 1e-3] / want[want > 1e-3]).max():.1e}")
     assert err.max() < TOL and np.all(err[want > 1e-3] <= 1e-9 * want[want > 1e-3]), (N, err.max())
     assert np.array_equal(got[1], np.full(200, got[1, 0]))                         # the sigma = 0 row: the nominal fidelity
 

@@ -1,5 +1,5 @@
 """`backend.mc_fidelity_times` / `mc_fidelity_times_philox` - the chain fidelity on a grid of readout times from one eigen
-decomposition per sample - on the device: the checks of times_checks.py (oracle with teeth on every (N, in, out) of its list,
+decomposition per sample - on the device: the checks of times_checks.py (oracle with teeth on every instantiation N = 2 ... 16,
 the closed-form spin-j chain, every output against its definition, tile boundaries, M = 1 and 64, a NaN row, shared draws,
 negative T a + b), slab j against the rows kernel BIT FOR BIT, torch tensors on a side stream, the kernel that generates its
 draws bit-identical to `philox_normal` + the tensor kernel, and the wrappers on top (`fidelity_readout_jitter_philox`,
@@ -33,21 +33,21 @@ def counted(be, run):
     return res
 
 
-@pytest.mark.parametrize("N,a,b", tc.PAIRS)
+@pytest.mark.parametrize("N,a,b", tc.EVERY_SIZE)
 def test_oracle_with_teeth(be, N, a, b):
     worst = cc.Worst()
     counted(be, lambda: tc.check_oracle(be, N, a, b, worst))
     print("times vs oracle:", (N, a, b), worst)
 
 
-@pytest.mark.parametrize("N", [3, 7, 16])
+@pytest.mark.parametrize("N", tc.STEP_SIZES)
 def test_closed_form(be, N):
     worst = cc.Worst()
     counted(be, lambda: tc.check_closed_form(be, N, worst))
     print("times vs closed form:", N, worst)
 
 
-@pytest.mark.parametrize("N,a,b", tc.PAIRS)
+@pytest.mark.parametrize("N,a,b", tc.EVERY_SIZE)
 def test_slabs_are_the_rows_kernel_bit_for_bit(be, N, a, b):
     """The same operations as mc_fidelity(kernel="tridiag_ql") at the row's time, so the same bits.  (The forced variant runs the
     textbook routine instead - another summation order: there the bound between two fp64 eigen routes of tests/test_gpu_grad.py,
@@ -69,7 +69,7 @@ def test_edges(be):
     counted(be, lambda: tc.check_edges(be))
 
 
-@pytest.mark.parametrize("N", (3, 7, 12))
+@pytest.mark.parametrize("N", tc.STEP_SIZES)
 def test_hard_inputs_need_no_fallback(be, N):
     """The inputs a spectral route is most likely to get wrong (grad_checks.hard_inputs: uniform and mirror-symmetric chains, a
     clustered spectrum, a cut bond, T = 0, biases of 1e3): the rows route has no condition on any of them - the product build
@@ -162,7 +162,7 @@ def fused(be, ctrl, K, N, a, b, offset, sigma, **grid):
 GRID = dict(tscale=tc.TSCALE, tshift=tc.TSHIFT, weights=np.array([0.1, 0.2, 0.4, 0.2, 0.1]))
 
 
-@pytest.mark.parametrize("N", (2, 3, 7, 12, 16))
+@pytest.mark.parametrize("N", tc.SIZES)
 def test_philox_is_bit_identical_to_the_two_kernel_route(be, N):
     """both parities of the first element, K = 65 (a full tile and a lane), a NaN row, a negative time entry"""
     ctrl = philox_rows(N)

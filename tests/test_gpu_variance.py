@@ -3,9 +3,20 @@ identity of every slab with the routes that exist (the fused Philox kernel for a
 tensors), the row means against the launch's own per-sample values and the exact identities of the special masks, the independent
 reference (oracle `fidelity_eigh` on `philox_host` hybrids), per-row sigma / static terms / far and wrapping offsets, the repair
 routes, and the layers above (`noise_variance_indices_philox`, `MCDataSim.get_variance_dict`).
-Shapes: C = 3 rows of `grad_checks.philox_ctrl` (one NaN row, one negative time), N in {2 (all-fp64), 3 (first mixed-precision
-size), 7 (headline; b held in LDS), 10 (a and b held in LDS), 13 (the limit; part of a in registers)}, K in {1, 63, 64, 65, 130}, an
-end-to-end pair (ends mode) and an interior pair (adjugate mode)."""
+Shapes: C = 3 rows of `grad_checks.philox_ctrl` (one NaN row, one negative time), K in {1, 63, 64, 65, 130} ({1, 65, 130} at N = 8, 9,
+11, 12), an end-to-end pair (ends mode) and an interior pair (adjugate mode), and EVERY instantiation N = 2 ... 13.  Where the kernel
+holds the two draw vectors a and b of a sample (`pickfreeze_reg_a`, `pickfreeze_reg_b`, `pickfreeze_min_waves`):
+    N = 2        a and b in registers, three waves per SIMD; all-fp64
+    N = 3        the same hold; the first mixed-precision size
+    N = 4, 5, 6  a and b in registers, two waves per SIMD
+    N = 7        a in registers, b in LDS, two waves (the headline size)
+    N = 8        the first size with a and b both in LDS, one wave
+    N = 9, 10    both in LDS
+    N = 11       both in LDS: the largest all-LDS footprint
+    N = 12       the only size with a split 4 coordinates in registers / 32 in LDS
+    N = 13       the limit: a split 10 in registers / 29 in LDS
+Long rows (K = 4096, 4097, 8193: more than one step of the row-mean kernel's loop over a row's tiles) and the ends of the group range
+(G = 0, 1, 64) follow the per-size tests."""
 import importlib
 
 import numpy as np
@@ -16,8 +27,12 @@ import variance_checks as vc
 
 pytestmark = pytest.mark.gpu
 vi = importlib.import_module("code-robchar_amd.variance_indices")
-SIZES = (2, 3, 7, 10, 13)
+SIZES = tuple(range(2, 14))
 KS = (1, 63, 64, 65, 130)
+
+
+def ks(N):
+    return (1, 65, 130) if N in (8, 9, 11, 12) else KS
 
 
 def pairs(N):
@@ -68,7 +83,7 @@ def test_bit_identity_with_the_routes_that_exist(be, dev, N):
     C = ctrl.shape[0]
     masks, *_ = vc.groups_under_test(N)
     ct = torch.as_tensor(ctrl, device=dev)
-    for K in KS:
+    for K in ks(N):
         for (a, b) in pairs(N):
             off = 7 + K                              # odd and even offsets, odd and even 3 N K
             off_b = off + C * K * 3 * N + 1
@@ -85,7 +100,7 @@ def test_bit_identity_with_the_routes_that_exist(be, dev, N):
 
 @pytest.mark.parametrize("N", SIZES)
 def test_means_against_own_slabs_and_exact_identities(be, N):
-    for K in KS:
+    for K in ks(N):
         for (a, b) in pairs(N):
             vc.check_means_against_own_slabs(be, N, K, a, b)
 
@@ -124,7 +139,7 @@ def test_reference_has_teeth_on_the_shipped_rows(be, lbfgs_n7):
     assert np.abs(got["fid"] - fid).max() < 1e-10 and err[:, :2].max() < 1e-10 and err[:, 2:].max() < vc.MEAN_ABS
 
 
-@pytest.mark.parametrize("N,offset", ((7, gc.FAR_OFFSET), (7, None), (10, None), (3, 2 ** 63 + 1)))
+@pytest.mark.parametrize("N,offset", ((7, gc.FAR_OFFSET), (7, None), (10, None), (3, 2 ** 63 + 1), (8, None), (12, None)))
 def test_row_sigma_static_terms_far_and_wrapping_offsets(be, dev, N, offset):
     """offset None: `grad_checks.wrap_offset` - the low word of the pair counter wraps inside the first tile of A"""
     import torch
@@ -152,7 +167,7 @@ def test_row_sigma_static_terms_far_and_wrapping_offsets(be, dev, N, offset):
         fused(be, ctrl, K, N, 0, N - 1, masks, far_a, 100)                      # inside A's range behind the wrap
 
 
-@pytest.mark.parametrize("N", (4, 10))
+@pytest.mark.parametrize("N", (4, 10, 12))
 def test_repair_routes_keep_the_bits(be, dev, N):
     """Inputs the tensor kernel already handles (tests/test_gpu_chain.py's hard cases): a mirror-symmetric controller on a chain
     cut in the middle (static coupling 0 there) with sigma = 0 has an exactly degenerate spectrum - the eigenvalue-only weights
@@ -174,6 +189,63 @@ def test_repair_routes_keep_the_bits(be, dev, N):
         print("repair", N, (a, b), tiles, "tiles")
         assert tiles > 0
         same_bits(got["fid"], tensor_route(be, dev, ctrl, K, N, a, b, masks, 0, off_b, sigma, None, h0o), ("repair, tensor route", N, a, b))
+        assert np.nanmax(got["fid"]) > 1e-3
+
+
+@pytest.mark.parametrize("N,K", ((2, 4096), (2, 4097), (3, 8193), (8, 4097)))
+def test_long_rows_through_the_row_mean_kernel(be, dev, N, K):
+    """more than 64 tiles per row: one tile per lane, a second step for lane 0 only, a third step, and the all-LDS hold"""
+    import torch
+    vc.check_long_rows(be, N, K, upload=lambda c: torch.as_tensor(c, device=dev))
+
+
+@pytest.mark.parametrize("N", (3, 10))
+def test_no_groups(be, dev, N):
+    """G = 0: slabs A and B only, three mean columns"""
+    import torch
+    vc.check_no_groups(be, N, upload=lambda c: torch.as_tensor(c, device=dev))
+
+
+@pytest.mark.parametrize("N", (3, 13))
+def test_one_group_of_the_top_coordinate(be, dev, N):
+    """G = 1, the mask of bit 3 N - 1 alone (the imaginary coupling below the last site)"""
+    ctrl = gc.philox_ctrl(N)
+    C, K = ctrl.shape[0], 65
+    masks = np.array([1 << (3 * N - 1)], dtype=np.uint64)
+    off, off_b = 4, 4 + C * K * 3 * N
+    for (a, b) in pairs(N):
+        got = fused(be, ctrl, K, N, a, b, masks, off, off_b)
+        assert got["fid"].shape == (3, C, K) and got["mean"].shape == (C, 5)
+        same_bits(got["fid"], tensor_route(be, dev, ctrl, K, N, a, b, masks, off, off_b, vc.SIGMA), ("G = 1, tensor route", N, a, b))
+        g = vc.assert_means_of_own_slabs(got, ~np.isnan(ctrl).any(axis=1), ("G = 1", N, a, b))
+        if (a, b) == (0, N - 1):
+            assert (g[:, 3] > 0.0).all() and (g[:, 4] > 0.0).all()          # the coordinate moves F, and is not all of the noise
+
+
+@pytest.mark.parametrize("K", (65, 130))
+def test_every_subset_of_the_coordinates_at_two_spins(be, dev, K):
+    """G = 64 at N = 2 - the full argument block, 66 slabs: the masks 0 ... 63 are every subset of the 6 coordinates"""
+    N = 2
+    vc.check_every_subset(be, K)
+    ctrl = gc.philox_ctrl(N)
+    masks = np.arange(64, dtype=np.uint64)
+    off, off_b = 5, 5 + ctrl.shape[0] * K * 3 * N + 7
+    for (a, b) in ((0, 1), (1, 0)):
+        got = fused(be, ctrl, K, N, a, b, masks, off, off_b, want=("fid",))
+        same_bits(got["fid"], tensor_route(be, dev, ctrl, K, N, a, b, masks, off, off_b, vc.SIGMA), ("every subset, tensor route", K, a, b))
+
+
+def test_sixty_four_groups_at_the_largest_size(be, dev):
+    """G = 64 at N = 13: every single coordinate and 25 random masks that reach into the mask's high word"""
+    N, K = 13, 65
+    ctrl = gc.philox_ctrl(N)
+    masks = vc.limit_masks()
+    off, off_b = 6, 6 + ctrl.shape[0] * K * 3 * N + 1
+    for (a, b) in pairs(N):
+        got = fused(be, ctrl, K, N, a, b, masks, off, off_b)
+        assert got["fid"].shape == (66, ctrl.shape[0], K)
+        same_bits(got["fid"], tensor_route(be, dev, ctrl, K, N, a, b, masks, off, off_b, vc.SIGMA), ("G = 64, tensor route", N, a, b))
+        vc.assert_means_of_own_slabs(got, ~np.isnan(ctrl).any(axis=1), ("G = 64", N, a, b))
         assert np.nanmax(got["fid"]) > 1e-3
 
 

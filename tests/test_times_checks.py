@@ -23,7 +23,23 @@ def test_oracle_workloads_have_teeth_and_pass(good, N, a, b):
     assert tc.check_against_rows_kernel(good, N, a, b) == 0.0
 
 
-@pytest.mark.parametrize("N", [3, 7, 16])
+@pytest.mark.parametrize("N,a,b", [p for p in tc.EVERY_SIZE if p not in tc.PAIRS])
+def test_every_size_has_teeth_and_passes(good, N, a, b):
+    """the sizes and pairs the GPU comparison adds to PAIRS: both guards hold on the reference (the margins are smaller than on
+    PAIRS: the worst median F is 0.034 and the worst spread 0.084, both at N = 15, 7 -> 6; the smallest share above 1e-3 is 0.981)"""
+    _, _, want = tc.oracle_workload(N, a, b)
+    spread = tc.check_reference_guards(want, (N, a, b))
+    print(f"N={N} ({a},{b}): median F {float(np.median(want)):.3f}, share > 1e-3 {float((want > 1e-3).mean()):.3f}, median spread {spread:.3f}")
+    tc.check_oracle(good, N, a, b)
+    assert tc.check_against_rows_kernel(good, N, a, b) == 0.0
+
+
+def test_every_size_is_listed():
+    assert {p[0] for p in tc.EVERY_SIZE} == set(range(2, 17)) and set(tc.PAIRS) <= set(tc.EVERY_SIZE) and len(tc.EVERY_SIZE) == 34
+    assert (2, 1, 0) in tc.EVERY_SIZE and (15, 7, 6) in tc.EVERY_SIZE
+
+
+@pytest.mark.parametrize("N", sorted(set(tc.STEP_SIZES) | {3, 7, 16}))
 def test_closed_form(good, N):
     tc.check_closed_form(good, N)
 

@@ -21,8 +21,15 @@ from oracle import robchar_oracle as orc
 # the grid of the oracle comparison: early and late readout, both signs of the shift
 TSCALE = np.array([0.8, 0.9, 1.0, 1.1, 1.2])
 TSHIFT = np.array([0.0, -0.25, 0.0, 0.25, 0.5])
-# (N, in, out) of the oracle comparison
+# (N, in, out) of the first oracle comparison: the pairs whose guard margins tests/test_times_checks.py records and on whose
+# controllers the teeth guards of grad_times_checks.py were measured
 PAIRS = ((2, 0, 1), (3, 0, 2), (7, 0, 6), (7, 2, 4), (7, 3, 3), (12, 0, 11), (12, 1, 7), (16, 0, 15), (16, 4, 9))
+# every instantiation of the kernels (N = 2 ... 16) with an end-to-end and an interior pair, then the further pairs of PAIRS; the
+# residency of the tensor kernel steps at N = 8 / 9 and 12 / 13 (`times_min_waves`), that of the kernel that generates its draws
+# drops to one wave at N = 14 (`times_philox_min_waves`)
+SIZES = tuple(range(2, 17))
+EVERY_SIZE = tuple(dict.fromkeys([(N, a, b) for N in SIZES for (a, b) in ((0, N - 1), (N // 2, max(N // 2 - 1, 0)))] + list(PAIRS)))
+STEP_SIZES = (3, 7, 8, 9, 12, 13, 14, 16)     # both sides of each residency step, and the one-wave sizes
 MIN_SPREAD = 0.05          # median over the samples of max_j F - min_j F on the reference: a kernel that ignores the grid fails
 
 
